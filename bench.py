@@ -18,6 +18,11 @@ the RCCL-broadcast path.
 Launch (driver contract):
   python bench.py --gpus N --steps K --warmup W
   torchrun --nnodes=1 --nproc-per-node N bench.py --gpus N ...
+
+Such a plain run only sets up, warms up, times the K steps and prints one
+JSON result line. --dump-outputs DIR adds a dump of what the last timed
+step materialized; --full is reserved for measurements beyond the headline
+figure.
 """
 
 import argparse
@@ -67,7 +72,83 @@ def get_args():
                         "tiny config, with the exact rank/env plumbing the "
                         "benchmark uses. Run it with the same launcher as "
                         "the benchmark (torchrun for N>1).")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write what the last timed "
+                        "step materialized (every parameter and buffer, or "
+                        "this rank's slices in mode=slice) as "
+                        "DIR/<name>.npy, float64 for float64/int64 tensors "
+                        "and float32 for the rest. The 64 MB total is "
+                        "split evenly over the tensors: one within its "
+                        "share is written whole in its own shape, a larger "
+                        "one as a 1-d fixed seeded sample of its elements "
+                        "(about 21k per tensor for Llama-3-70B). *.npy "
+                        "files already in DIR are removed first. "
+                        "Inputs are seeded, so two "
+                        "builds run with the same arguments can be compared "
+                        "output for output. Ranks above 0 write under "
+                        "DIR/rank<r>/.")
+    p.add_argument("--full", action="store_true",
+                   help="also run whatever the benchmark measures beyond "
+                        "its headline figure. A plain run only sets up, "
+                        "warms up, times the steps and prints the result "
+                        "line; today there is nothing beyond that, so "
+                        "--full changes nothing (the preflight stays "
+                        "behind --selftest).")
     return p.parse_args()
+
+
+# --dump-outputs writes at most this much array data (the limit is 64 MB;
+# the rest is headroom for the .npy headers).
+DUMP_BUDGET_BYTES = 60 << 20
+# A sampled tensor always includes this many leading and trailing elements,
+# where partial tiles and tail handling live.
+DUMP_EDGE = 1024
+
+
+def named_outputs(out):
+    """(name, tensor) for everything a caller of the timed path receives:
+    the slice dict of mode=slice, else the module's materialized parameters
+    and buffers (mode=shard leaves the tensors other ranks own fake)."""
+    from torchdistx_amd import is_fake
+
+    if isinstance(out, dict):
+        return sorted(out.items())
+    named = list(out.named_parameters()) + list(out.named_buffers())
+    return [(n, t) for n, t in named if not is_fake(t)]
+
+
+def dump_outputs(out_dir, named, budget_bytes=DUMP_BUDGET_BYTES):
+    """Write each tensor as out_dir/<name>.npy. The budget is split evenly:
+    a tensor within its share is written whole in its own shape, a larger
+    one as a sorted 1-d sample of its flattened elements, the edges plus
+    indices drawn from a generator seeded by the tensor's name."""
+    import zlib
+
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    # Arrays of an earlier dump (another model or mode) must not mix in.
+    for f in os.listdir(out_dir):
+        if f.endswith(".npy"):
+            os.remove(os.path.join(out_dir, f))
+    share = budget_bytes // max(len(named), 1)
+    for name, t in named:
+        t = t.detach()
+        wide = t.dtype in (torch.float64, torch.int64)
+        out_dtype = torch.float64 if wide else torch.float32
+        cap = share // out_dtype.itemsize
+        if t.numel() > cap:
+            n = t.numel()
+            edge = min(DUMP_EDGE, cap // 4)
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.cat([
+                torch.arange(edge),
+                torch.randint(n, (cap - 2 * edge,), generator=g),
+                torch.arange(n - edge, n),
+            ]).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"),
+                t.to(out_dtype).cpu().numpy())
 
 
 def main():
@@ -143,7 +224,7 @@ def main():
             )
             sys.exit(1)
 
-    def one_step(seed: int) -> None:
+    def one_step(seed: int, keep: bool = False):
         torch.manual_seed(seed)
         module = deferred_init(build_model, cfg, device=device, dtype=dtype)
         if args.mode == "slice":
@@ -151,6 +232,8 @@ def main():
             # contiguous dim-0 row-slice of every parameter.
             shards = materialize_module_dim0_sharded(module, rank, world)
             assert shards
+            if keep:
+                return shards
             del shards
         elif args.mode == "replicate" and use_cuda and args.replay == "batched":
             from torchdistx_amd.deferred_init import (
@@ -172,6 +255,8 @@ def main():
                 assert not is_deferred(module), "materialization incomplete"
         # Reference-counting frees the module and its tape immediately (the
         # tape's ownership graph is acyclic by design); no gc.collect().
+        if keep:
+            return module
         del module
 
     def barrier_sync():
@@ -185,10 +270,23 @@ def main():
     barrier_sync()
 
     t0 = time.perf_counter()
+    last = None
     for i in range(args.steps):
-        one_step(seed=2000 + i)
+        last = one_step(seed=2000 + i,
+                        keep=bool(args.dump_outputs) and i == args.steps - 1)
     barrier_sync()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs:
+        out_dir = args.dump_outputs
+        if rank > 0:
+            out_dir = os.path.join(out_dir, f"rank{rank}")
+        dump_outputs(out_dir, named_outputs(last))
+        # The kept step has not freed its module yet; every other step pays
+        # for that inside the timed window, so this one is charged too.
+        t_free = time.perf_counter()
+        del last
+        elapsed += time.perf_counter() - t_free
 
     # MAX over ranks.
     if distributed:

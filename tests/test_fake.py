@@ -2,8 +2,8 @@
 # teardown, ops/views/autograd on fake tensors, meta_like metadata, the
 # documented output-device heuristic (explicit device arg -> common
 # tensor device -> CPU, with the 0-dim CPU scalar exemption), and repr.
-# The reference's own suite additionally runs unmodified through
-# tests/test_reference_suite.py.
+# tests/test_reference_suite.py checks that the `torchdistx` alias exports
+# these very objects.
 
 import pytest
 import torch
