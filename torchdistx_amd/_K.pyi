@@ -8,6 +8,7 @@ def has_init_kernels() -> bool: ...
 def has_anyprecision_adamw() -> bool: ...
 def has_anyprecision_adamw_batched() -> bool: ...
 def has_batched_init() -> bool: ...
+def has_fused_chains() -> bool: ...
 def anyprecision_adamw_(
     param: torch.Tensor,
     grad: torch.Tensor,
@@ -43,4 +44,7 @@ def batched_init_(
     p1s: List[float],
     seeds: List[int],
     offsets: List[int],
+    tail_ops: List[List[int]] = ...,
+    tail_s0: List[List[float]] = ...,
+    tail_s1: List[List[float]] = ...,
 ) -> None: ...

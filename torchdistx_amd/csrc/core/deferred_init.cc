@@ -20,9 +20,11 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <condition_variable>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <optional>
@@ -1153,7 +1155,128 @@ struct ChainStep {
   std::vector<c10::IValue> pointwise_args;  // non-self args for kPointwise
   // Replay closure of the recorded op (boxed call), for kPointwise.
   std::function<void(torch::jit::Stack&)> pointwise_run;
+  // Set for a kPointwise step the RNG kernels can apply in registers
+  // (fusableTailOp below).
+  std::optional<TailOp> tail_op;
 };
+
+// A recorded scalar operand of a fusable tail step. Only what ATen turns
+// into an opmath_t immediate qualifies: Scalar IValues and wrapped-number
+// 0-dim CPU tensors (python scalars). Any other 0-dim tensor operand
+// takes part in type promotion differently and is left to ATen.
+struct TailOperand {
+  bool present = false;  // false: None
+  double value = 0.0;
+};
+
+std::optional<TailOperand> tailOperand(const c10::IValue& v) {
+  TailOperand out;
+  if (v.isNone()) {
+    return out;
+  }
+  out.present = true;
+  if (v.isDouble()) {
+    out.value = v.toDouble();
+    return out;
+  }
+  if (v.isInt()) {
+    out.value = static_cast<double>(v.toInt());
+    return out;
+  }
+  if (v.isTensor()) {
+    const at::Tensor& t = v.toTensor();
+    if (!t.defined() || isFake(t) || t.dim() != 0 || !t.is_cpu() ||
+        !t.unsafeGetTensorImpl()->is_wrapped_number()) {
+      return std::nullopt;
+    }
+    // Wrapped python numbers are double or int64 (bool and complex ones
+    // are not immediates of these ops). Read in place: no dispatch.
+    if (t.scalar_type() == at::kDouble) {
+      out.value = *t.const_data_ptr<double>();
+    } else if (t.scalar_type() == at::kLong) {
+      out.value = static_cast<double>(*t.const_data_ptr<int64_t>());
+    } else {
+      return std::nullopt;
+    }
+    return out;
+  }
+  return std::nullopt;  // bool, complex, symbolic, lists, ...
+}
+
+// Maps a kPointwise step to its TailOp when the fused kernels reproduce
+// ATen's bits for it. div_/sqrt_/reciprocal_ are excluded (ATen divides
+// by a scalar through a host-computed reciprocal), as is any add_/sub_
+// with alpha != 1 (ATen may or may not contract a + alpha * b).
+std::optional<TailOp> fusableTailOp(const std::string& name,
+                                    const std::vector<c10::IValue>& args) {
+  std::vector<TailOperand> a;
+  for (const c10::IValue& v : args) {
+    auto operand = tailOperand(v);
+    if (!operand.has_value() ||
+        (operand->present && std::isnan(operand->value))) {
+      return std::nullopt;
+    }
+    a.push_back(*operand);
+  }
+  auto unary = [&](TailOp::Code code) -> std::optional<TailOp> {
+    if (!a.empty()) {
+      return std::nullopt;
+    }
+    return TailOp{code, 0.0, 0.0};
+  };
+  auto one = [&](TailOp::Code code) -> std::optional<TailOp> {
+    if (a.size() != 1 || !a[0].present) {
+      return std::nullopt;
+    }
+    return TailOp{code, a[0].value, 0.0};
+  };
+  if (name == "aten::erfinv_") {
+    return unary(TailOp::kErfinv);
+  }
+  if (name == "aten::neg_") {
+    return unary(TailOp::kNeg);
+  }
+  if (name == "aten::abs_") {
+    return unary(TailOp::kAbs);
+  }
+  if (name == "aten::mul_") {
+    // mul_.Tensor with a wrapped number only (what `t.mul_(2.0)`
+    // records): mul_.Scalar puts the scalar first, and ATen's CPU kernel
+    // then rounds it to a 16-bit tensor dtype before multiplying.
+    if (args.size() != 1 || !args[0].isTensor()) {
+      return std::nullopt;
+    }
+    return one(TailOp::kMul);
+  }
+  if (name == "aten::clamp_min_") {
+    return one(TailOp::kClampMin);
+  }
+  if (name == "aten::clamp_max_") {
+    return one(TailOp::kClampMax);
+  }
+  if (name == "aten::add_" || name == "aten::sub_") {
+    if (a.size() != 2 || !a[0].present || !a[1].present ||
+        a[1].value != 1.0) {
+      return std::nullopt;
+    }
+    return TailOp{name == "aten::add_" ? TailOp::kAdd : TailOp::kSub,
+                  a[0].value, 0.0};
+  }
+  if (name == "aten::clamp_") {
+    if (a.size() != 2 || (!a[0].present && !a[1].present)) {
+      return std::nullopt;
+    }
+    // A one-sided clamp_ is ATen's clamp_min/clamp_max kernel.
+    if (!a[1].present) {
+      return TailOp{TailOp::kClampMin, a[0].value, 0.0};
+    }
+    if (!a[0].present) {
+      return TailOp{TailOp::kClampMax, a[1].value, 0.0};
+    }
+    return TailOp{TailOp::kClamp, a[0].value, a[1].value};
+  }
+  return std::nullopt;
+}
 
 // In-place elementwise ops whose only parameters are scalars; slicing
 // commutes with all of them.
@@ -1254,6 +1377,7 @@ ChainStep classifyChainNode(const OpNode& node) {
     step.kind = ChainStep::Kind::kPointwise;
     step.pointwise_args.assign(op.args.begin() + 1, op.args.end());
     step.pointwise_run = op.run;
+    step.tail_op = fusableTailOp(op.name, step.pointwise_args);
   } else {
     TORCH_CHECK(false, "slice materialization: `", op.name,
                 "` is not a whole-tensor init op; materialize the tensor "
@@ -1364,16 +1488,98 @@ void applyShardStep(const ChainStep& step, at::Tensor& shard,
   }
 }
 
-}  // namespace
+int64_t rngDistCode(ChainStep::Kind kind) {
+  return kind == ChainStep::Kind::kUniform
+             ? 0
+             : (kind == ChainStep::Kind::kNormal ? 1 : 2);
+}
 
-// Reduces a deferred tensor's tape chain to its final whole-tensor value
-// step, when the chain is that simple. Every simple-chain value step
-// (uniform/normal/bernoulli/fill/zero) overwrites the whole tensor, so
-// only the LAST one determines the bits: batched replay can then fill
-// many tensors with ONE kernel launch. Returns nullopt for anything
-// else (pointwise tails, views, cross-tensor deps, explicit
-// generators); callers fall back to ordinary materialization.
-std::optional<InitPlan> tensorInitPlan(const at::Tensor& tensor) {
+// One launch for an RNG step and the fusable tail after it: the window
+// op draws the values and applies the tail before its single store.
+void applyFusedShardStep(const ChainStep& rng, const std::vector<TailOp>& tail,
+                         at::Tensor& shard, const ShardWindow& w,
+                         int64_t full_numel) {
+  TORCH_CHECK(rng.philox.has_value(),
+              "slice materialization: this RNG op carries no pinned "
+              "Philox state (was it recorded by an older build?)");
+  static const auto chain_shard_win =
+      c10::Dispatcher::singleton()
+          .findSchemaOrThrow("tdx::rng_chain_shard_win_", "")
+          .typed<at::Tensor&(at::Tensor&, int64_t, int64_t, int64_t, int64_t,
+                             int64_t, double, double, at::IntArrayRef,
+                             at::ArrayRef<double>, at::ArrayRef<double>,
+                             int64_t, int64_t, int64_t)>();
+  std::vector<int64_t> ops;
+  std::vector<double> s0;
+  std::vector<double> s1;
+  for (const TailOp& t : tail) {
+    ops.push_back(t.op);
+    s0.push_back(t.s0);
+    s1.push_back(t.s1);
+  }
+  chain_shard_win.call(shard, w.n_blocks, w.block_len, w.g_stride, w.g_off,
+                       rngDistCode(rng.kind), rng.p0, rng.p1, ops, s0, s1,
+                       full_numel, static_cast<int64_t>(rng.philox->first),
+                       static_cast<int64_t>(rng.philox->second));
+}
+
+// Whether `op` on a tensor of `dtype` and `numel` elements may fuse in
+// the current switch state: everything in the fusable set, except the
+// steps that are NOT bitwise equal to ATen's kernels on gfx950, which
+// need the explicit opt-in (fusedInitChainsExplicit):
+//  * erfinv_ on float32: 1-2 ulp on about half of all inputs.
+//  * mul_ on float16 tensors of 2^31 elements or more. ATen's f16
+//    multiply rounds differently in the last, partial block of its
+//    elementwise kernel; the fused kernels reproduce that from the
+//    tensor's element count (csrc/hip/init_kernels.hip tailMul), but
+//    ATen splits tensors too large for 32-bit indexing into several
+//    launches, whose block boundaries are not reproduced.
+bool tailOpAdmitted(const TailOp& op, c10::ScalarType dtype, int64_t numel) {
+  const bool inexact =
+      (op.op == TailOp::kErfinv && dtype == at::kFloat) ||
+      (op.op == TailOp::kMul && dtype == at::kHalf &&
+       numel > std::numeric_limits<int32_t>::max());
+  return !inexact || fusedInitChainsExplicit();
+}
+
+bool isRngStep(const ChainStep& step) {
+  return step.kind == ChainStep::Kind::kUniform ||
+         step.kind == ChainStep::Kind::kNormal ||
+         step.kind == ChainStep::Kind::kBernoulli;
+}
+
+// Index of the RNG step of a trailing run [RNG step, fusable tail...,
+// pass steps...] that one fused launch can serve, or nullopt when the
+// chain does not end that way.
+std::optional<size_t> fusedRunStart(const std::vector<ChainStep>& steps,
+                                    c10::ScalarType dtype, int64_t numel) {
+  if (!fusedInitChainsEnabled() ||
+      (dtype != at::kFloat && dtype != at::kBFloat16 && dtype != at::kHalf)) {
+    return std::nullopt;
+  }
+  size_t end = steps.size();
+  while (end > 0 && steps[end - 1].kind == ChainStep::Kind::kPass) {
+    --end;
+  }
+  size_t first_tail = end;
+  while (first_tail > 0 &&
+         steps[first_tail - 1].kind == ChainStep::Kind::kPointwise &&
+         steps[first_tail - 1].tail_op.has_value() &&
+         tailOpAdmitted(*steps[first_tail - 1].tail_op, dtype, numel)) {
+    --first_tail;
+  }
+  const size_t n_tail = end - first_tail;
+  if (n_tail == 0 || n_tail > kMaxTailOps || first_tail == 0 ||
+      !isRngStep(steps[first_tail - 1]) ||
+      !steps[first_tail - 1].philox.has_value()) {
+    return std::nullopt;
+  }
+  return first_tail - 1;
+}
+
+// Shared body of tensorInitPlan (allow_tail == false) and tensorChainPlan.
+std::optional<ChainPlan> chainPlanImpl(const at::Tensor& tensor,
+                                       bool allow_tail) {
   auto* fake = asFake(tensor);
   if (fake == nullptr) {
     return std::nullopt;
@@ -1387,10 +1593,11 @@ std::optional<InitPlan> tensorInitPlan(const at::Tensor& tensor) {
     return std::nullopt;
   }
   std::lock_guard<std::recursive_mutex> lock{tape_mutex};
-  InitPlan plan;
+  ChainPlan plan;
   try {
     auto nodes = buildCallStack(*rec);
     bool have_value = false;
+    bool tail_unfusable = false;  // a live pointwise step we cannot fuse
     for (const auto& n : nodes) {
       ChainStep step = classifyChainNode(*n);
       switch (step.kind) {
@@ -1398,15 +1605,29 @@ std::optional<InitPlan> tensorInitPlan(const at::Tensor& tensor) {
         case ChainStep::Kind::kPass:
           break;
         case ChainStep::Kind::kPointwise:
-          return std::nullopt;  // needs sequential application
+          if (!allow_tail) {
+            return std::nullopt;  // needs sequential application
+          }
+          if (step.tail_op.has_value() &&
+              tailOpAdmitted(*step.tail_op, meta.scalar_type(),
+                             meta.numel())) {
+            plan.tail.push_back(*step.tail_op);
+          } else {
+            tail_unfusable = true;
+          }
+          break;
         case ChainStep::Kind::kZero:
           plan.kind = InitPlan::Kind::kZero;
           have_value = true;
+          plan.tail.clear();
+          tail_unfusable = false;
           break;
         case ChainStep::Kind::kFill:
           plan.kind = InitPlan::Kind::kFill;
           plan.p0 = step.p0;
           have_value = true;
+          plan.tail.clear();
+          tail_unfusable = false;
           break;
         case ChainStep::Kind::kUniform:
         case ChainStep::Kind::kNormal:
@@ -1424,11 +1645,23 @@ std::optional<InitPlan> tensorInitPlan(const at::Tensor& tensor) {
           plan.seed = step.philox->first;
           plan.offset = step.philox->second;
           have_value = true;
+          // Everything before a whole-tensor value step is dead.
+          plan.tail.clear();
+          tail_unfusable = false;
           break;
       }
     }
     if (!have_value) {
       plan.kind = InitPlan::Kind::kFactory;  // allocate-only (empty)
+    }
+    if (tail_unfusable || !plan.tail.empty()) {
+      // A live tail fuses only into a pinned-Philox RNG kernel.
+      const bool rng_head = plan.kind == InitPlan::Kind::kUniform ||
+                            plan.kind == InitPlan::Kind::kNormal ||
+                            plan.kind == InitPlan::Kind::kBernoulli;
+      if (tail_unfusable || !rng_head || plan.tail.size() > kMaxTailOps) {
+        return std::nullopt;
+      }
     }
   } catch (const c10::Error&) {
     return std::nullopt;  // not a simple chain
@@ -1438,6 +1671,35 @@ std::optional<InitPlan> tensorInitPlan(const at::Tensor& tensor) {
   plan.device = fake->fake_device();
   plan.requires_grad = tensor.requires_grad();
   return plan;
+}
+
+}  // namespace
+
+const char* tailOpName(int32_t op) {
+  static const char* kNames[] = {"erfinv",    "mul",       "add",
+                                 "sub",       "clamp",     "clamp_min",
+                                 "clamp_max", "neg",       "abs"};
+  TORCH_CHECK(0 <= op && op < 9, "bad tail opcode ", op);
+  return kNames[op];
+}
+
+// Reduces a deferred tensor's tape chain to its final whole-tensor value
+// step, when the chain is that simple. Every simple-chain value step
+// (uniform/normal/bernoulli/fill/zero) overwrites the whole tensor, so
+// only the LAST one determines the bits: batched replay can then fill
+// many tensors with ONE kernel launch. Returns nullopt for anything
+// else (pointwise tails, views, cross-tensor deps, explicit
+// generators); callers fall back to ordinary materialization.
+std::optional<InitPlan> tensorInitPlan(const at::Tensor& tensor) {
+  auto plan = chainPlanImpl(tensor, /*allow_tail=*/false);
+  if (!plan.has_value()) {
+    return std::nullopt;
+  }
+  return static_cast<const InitPlan&>(*plan);
+}
+
+std::optional<ChainPlan> tensorChainPlan(const at::Tensor& tensor) {
+  return chainPlanImpl(tensor, fusedInitChainsEnabled());
 }
 
 at::Tensor materializeTensorShard(const at::Tensor& tensor,
@@ -1494,8 +1756,22 @@ at::Tensor materializeTensorShard(const at::Tensor& tensor,
       shard_sizes, at::TensorOptions()
                        .dtype(meta.scalar_type())
                        .device(fake->fake_device()));
-  for (const ChainStep& step : steps) {
-    applyShardStep(step, shard, w);
+  // A trailing [RNG step, fusable tail...] run is one fused launch; any
+  // other arrangement applies step by step.
+  const std::optional<size_t> fused_at =
+      fusedRunStart(steps, meta.scalar_type(), meta.numel());
+  for (size_t i = 0; i < steps.size(); ++i) {
+    if (fused_at.has_value() && i == *fused_at) {
+      std::vector<TailOp> tail;
+      for (++i; i < steps.size() &&
+                steps[i].kind == ChainStep::Kind::kPointwise;
+           ++i) {
+        tail.push_back(*steps[i].tail_op);
+      }
+      applyFusedShardStep(steps[*fused_at], tail, shard, w, meta.numel());
+      break;  // only pass steps remain
+    }
+    applyShardStep(steps[i], shard, w);
   }
   return shard;
 }

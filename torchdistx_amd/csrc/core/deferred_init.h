@@ -73,6 +73,49 @@ struct InitPlan {
 
 std::optional<InitPlan> tensorInitPlan(const at::Tensor& tensor);
 
+// One step of a fused pointwise-scalar tail (see tensorChainPlan). The
+// opcode numbering is shared with the tdx::rng_chain_ ops and the CDNA4
+// kernels (csrc/hip/init_kernels.hip applyTail). s0/s1 hold the recorded
+// scalars as doubles; the kernels narrow them to float the way ATen
+// narrows a scalar operand to opmath_t.
+struct TailOp {
+  enum Code : int32_t {
+    kErfinv = 0,
+    kMul = 1,       // s0
+    kAdd = 2,       // s0 (alpha == 1 only)
+    kSub = 3,       // s0 (alpha == 1 only)
+    kClamp = 4,     // s0 = min, s1 = max
+    kClampMin = 5,  // s0
+    kClampMax = 6,  // s0
+    kNeg = 7,
+    kAbs = 8,
+  };
+  int32_t op = kErfinv;
+  double s0 = 0.0;
+  double s1 = 0.0;
+};
+
+constexpr size_t kMaxTailOps = 8;
+
+// Name of a TailOp code ("erfinv", "mul", ...).
+const char* tailOpName(int32_t op);
+
+// InitPlan plus the fusable pointwise tail that follows the plan's value
+// step (empty for chains tensorInitPlan already reduces).
+struct ChainPlan : InitPlan {
+  std::vector<TailOp> tail;
+};
+
+// Like tensorInitPlan, but a chain whose last whole-tensor value step is
+// a pinned-Philox RNG step followed only by fusable pointwise-scalar ops
+// (erfinv_/mul_/add_/sub_/clamp*_/neg_/abs_ with Scalar or wrapped-number
+// operands, alpha == 1, at most kMaxTailOps of them) is plannable too:
+// the tail runs in registers inside the RNG kernel. Pointwise steps
+// before the last value step are dead and dropped. With
+// fusedInitChainsEnabled() off, any pointwise step makes the chain
+// unplannable, as in tensorInitPlan.
+std::optional<ChainPlan> tensorChainPlan(const at::Tensor& tensor);
+
 // Slice materialization: materializes indices [start_row, end_row) of
 // the deferred tensor along `dim` WITHOUT materializing the rest,
 // bitwise-equal to the corresponding slice of a full materialization

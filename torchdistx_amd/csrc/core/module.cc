@@ -134,6 +134,45 @@ PYBIND11_MODULE(_C, m) {
      "value step), or None when the tape is not that simple. Feeds the "
      "batched replay planner (materialize_module_batched).");
 
+  m.def("set_fused_init_chains", &tdx::setFusedInitChains,
+        pybind11::arg("enabled"));
+  m.def("fused_init_chains_enabled", &tdx::fusedInitChainsEnabled);
+  m.def("reset_fused_init_chains", &tdx::resetFusedInitChains,
+        "Back to the start-up state: TDX_FUSED_INIT_CHAINS if set, else on "
+        "by default (not explicitly).");
+  m.def("fused_init_chains_explicit", &tdx::fusedInitChainsExplicit,
+        "True once fusion was switched on explicitly; only then does what "
+        "is not bitwise equal to ATen's kernels fuse: erfinv_ on float32 "
+        "(and float16 mul_ on tensors of 2^31 elements or more).");
+
+  m.def("tensor_chain_plan", [](const at::Tensor& t) -> pybind11::object {
+    auto plan = tdx::tensorChainPlan(t);
+    if (!plan.has_value()) {
+      return pybind11::none();
+    }
+    static const char* kKinds[] = {"factory", "uniform", "normal",
+                                   "bernoulli", "fill", "zero"};
+    pybind11::dict d;
+    d["kind"] = kKinds[static_cast<int>(plan->kind)];
+    d["p0"] = plan->p0;
+    d["p1"] = plan->p1;
+    d["seed"] = static_cast<int64_t>(plan->seed);
+    d["offset"] = static_cast<int64_t>(plan->offset);
+    d["sizes"] = plan->sizes;
+    d["dtype"] = pybind11::cast(plan->dtype);
+    d["device"] = pybind11::cast(plan->device);
+    d["requires_grad"] = plan->requires_grad;
+    pybind11::list tail;
+    for (const tdx::TailOp& op : plan->tail) {
+      tail.append(pybind11::make_tuple(tdx::tailOpName(op.op), op.s0, op.s1));
+    }
+    d["tail"] = tail;
+    return d;
+  }, "tensor_init_plan plus \"tail\": the fusable pointwise-scalar ops "
+     "[(name, s0, s1), ...] that follow the plan's RNG value step and run "
+     "inside its kernel. None when the chain is not plannable, or has a "
+     "tail while fused init chains are switched off.");
+
   m.def("materialize_tensor_shard",
         [](const at::Tensor& t, int64_t start_row, int64_t end_row,
            int64_t dim) {

@@ -10,6 +10,18 @@ namespace {
 std::atomic<bool> native_init_enabled{true};
 std::atomic<bool> native_init_cpu_enabled{false};
 
+// 0: off. 1: on by default. 2: switched on explicitly, which also admits
+// the f32 erfinv step (see fusedInitChainsExplicit).
+int fusedInitChainsDefault() {
+  const char* v = std::getenv("TDX_FUSED_INIT_CHAINS");
+  if (v == nullptr) {
+    return 1;
+  }
+  return std::strcmp(v, "0") == 0 ? 0 : 2;
+}
+
+std::atomic<int> fused_init_chains_mode{fusedInitChainsDefault()};
+
 struct Redirect {
   const char* aten_name;
   const char* aten_overload;
@@ -47,6 +59,23 @@ void setNativeInitCpuEnabled(bool enabled) noexcept {
 
 bool nativeInitCpuEnabled() noexcept {
   return native_init_cpu_enabled.load(std::memory_order_relaxed);
+}
+
+void setFusedInitChains(bool enabled) noexcept {
+  fused_init_chains_mode.store(enabled ? 2 : 0, std::memory_order_relaxed);
+}
+
+void resetFusedInitChains() noexcept {
+  fused_init_chains_mode.store(fusedInitChainsDefault(),
+                               std::memory_order_relaxed);
+}
+
+bool fusedInitChainsEnabled() noexcept {
+  return fused_init_chains_mode.load(std::memory_order_relaxed) != 0;
+}
+
+bool fusedInitChainsExplicit() noexcept {
+  return fused_init_chains_mode.load(std::memory_order_relaxed) == 2;
 }
 
 bool tryNativeInitRedirect(

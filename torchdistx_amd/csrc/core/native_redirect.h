@@ -42,4 +42,20 @@ bool nativeInitEnabled() noexcept;
 void setNativeInitCpuEnabled(bool enabled) noexcept;
 bool nativeInitCpuEnabled() noexcept;
 
+// Fusing an RNG value step with its pointwise-scalar tail into one kernel
+// (tensorChainPlan, materializeTensorShard). On by default; the
+// environment variable TDX_FUSED_INIT_CHAINS=0 starts the process with it
+// off. Off means tails are applied one ATen op at a time.
+void setFusedInitChains(bool enabled) noexcept;
+bool fusedInitChainsEnabled() noexcept;
+// True once fusion was asked for explicitly (setFusedInitChains(true) or
+// TDX_FUSED_INIT_CHAINS=1). What is not bitwise equal to unfused replay
+// fuses only then: erfinv_ on a float32 tensor (ATen's f32 erfinv kernel
+// and the device library's erfinvf differ by 1-2 ulp on about half of
+// all inputs; on bf16/fp16 tensors they agree), and float16 mul_
+// on tensors of 2^31 elements or more (see tailOpAdmitted).
+bool fusedInitChainsExplicit() noexcept;
+// Back to the start-up state (TDX_FUSED_INIT_CHAINS, else on by default).
+void resetFusedInitChains() noexcept;
+
 }  // namespace tdx

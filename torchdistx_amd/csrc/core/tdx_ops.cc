@@ -16,8 +16,10 @@
 #include <type_traits>
 
 #include <ATen/ATen.h>
+#include <ATen/ScalarOps.h>
 #include <torch/library.h>
 
+#include "deferred_init.h"
 #include "philox.h"
 
 namespace tdx {
@@ -305,6 +307,105 @@ at::Tensor& cpu_bernoulli_shard_win_(at::Tensor& shard, int64_t n_blocks,
   return shard;
 }
 
+// ---- fused RNG + pointwise-tail ops ---------------------------------------
+// CPU form: the Philox fill above, then the same ATen in-place ops the
+// unfused replay would run, in order — bitwise equal to it by
+// construction. It exists so the planner and slice plumbing are testable
+// without a GPU; the CDNA4 kernels apply the tail in registers instead.
+
+void cpuCheckTail(at::IntArrayRef tail_ops, at::ArrayRef<double> tail_s0,
+                  at::ArrayRef<double> tail_s1) {
+  TORCH_CHECK(tail_ops.size() <= kMaxTailOps &&
+                  tail_s0.size() == tail_ops.size() &&
+                  tail_s1.size() == tail_ops.size(),
+              "rng_chain: at most ", kMaxTailOps,
+              " tail ops, with one s0 and one s1 each");
+}
+
+void cpuApplyTail(at::Tensor& self, at::IntArrayRef tail_ops,
+                  at::ArrayRef<double> tail_s0,
+                  at::ArrayRef<double> tail_s1) {
+  for (size_t i = 0; i < tail_ops.size(); ++i) {
+    const double s0 = tail_s0[i];
+    const double s1 = tail_s1[i];
+    switch (tail_ops[i]) {
+      case TailOp::kErfinv:
+        self.erfinv_();
+        break;
+      case TailOp::kMul:
+        // The mul_.Tensor overload with a wrapped number, which is what
+        // `t.mul_(2.0)` records: mul_.Scalar rounds the scalar to a
+        // 16-bit dtype first on CPU, so it is not in the fusable set.
+        self.mul_(at::native::wrapped_scalar_tensor(s0));
+        break;
+      case TailOp::kAdd:
+        self.add_(s0);
+        break;
+      case TailOp::kSub:
+        self.sub_(s0);
+        break;
+      case TailOp::kClamp:
+        self.clamp_(s0, s1);
+        break;
+      case TailOp::kClampMin:
+        self.clamp_min_(s0);
+        break;
+      case TailOp::kClampMax:
+        self.clamp_max_(s0);
+        break;
+      case TailOp::kNeg:
+        self.neg_();
+        break;
+      case TailOp::kAbs:
+        self.abs_();
+        break;
+      default:
+        TORCH_CHECK(false, "rng_chain: bad tail opcode ", tail_ops[i]);
+    }
+  }
+}
+
+at::Tensor& cpu_rng_chain_shard_win_(
+    at::Tensor& shard, int64_t n_blocks, int64_t block_len, int64_t g_stride,
+    int64_t g_off, int64_t dist, double p0, double p1,
+    at::IntArrayRef tail_ops, at::ArrayRef<double> tail_s0,
+    at::ArrayRef<double> tail_s1, int64_t full_numel, int64_t seed,
+    int64_t offset) {
+  // full_numel places ATen's position-dependent f16 mul rounding in the
+  // GPU kernels; ATen's CPU kernels have none.
+  (void)full_numel;
+  cpuCheckTail(tail_ops, tail_s0, tail_s1);
+  switch (dist) {
+    case 0:
+      cpu_uniform_shard_win_(shard, n_blocks, block_len, g_stride, g_off, p0,
+                             p1, seed, offset);
+      break;
+    case 1:
+      cpu_normal_shard_win_(shard, n_blocks, block_len, g_stride, g_off, p0,
+                            p1, seed, offset);
+      break;
+    case 2:
+      cpu_bernoulli_shard_win_(shard, n_blocks, block_len, g_stride, g_off,
+                               p0, seed, offset);
+      break;
+    default:
+      TORCH_CHECK(false, "rng_chain: dist must be 0 (uniform), 1 (normal) "
+                         "or 2 (bernoulli), got ", dist);
+  }
+  cpuApplyTail(shard, tail_ops, tail_s0, tail_s1);
+  return shard;
+}
+
+at::Tensor& cpu_rng_chain_(at::Tensor& self, int64_t dist, double p0,
+                           double p1, at::IntArrayRef tail_ops,
+                           at::ArrayRef<double> tail_s0,
+                           at::ArrayRef<double> tail_s1, int64_t seed,
+                           int64_t offset) {
+  return cpu_rng_chain_shard_win_(self, 1, self.numel(), self.numel(), 0,
+                                  dist, p0, p1, tail_ops, tail_s0, tail_s1,
+                                  self.numel(), seed, offset);
+}
+
 TORCH_LIBRARY(tdx, m) {
   m.def(
       "uniform_(Tensor(a!) self, float from=0., float to=1., *, "
@@ -344,6 +445,19 @@ TORCH_LIBRARY(tdx, m) {
       "bernoulli_shard_win_(Tensor(a!) shard, int n_blocks, int block_len, "
       "int g_stride, int g_off, float p=0.5, *, int seed, int offset) "
       "-> Tensor(a!)");
+  // dist: 0 uniform (p0, p1 = from, to), 1 normal (mean, std),
+  // 2 bernoulli (p, unused); tail_ops are TailOp codes (deferred_init.h);
+  // full_numel is the element count of the full tensor the window is
+  // cut from.
+  m.def(
+      "rng_chain_(Tensor(a!) self, int dist, float p0, float p1, "
+      "int[] tail_ops, float[] tail_s0, float[] tail_s1, *, int seed, "
+      "int offset) -> Tensor(a!)");
+  m.def(
+      "rng_chain_shard_win_(Tensor(a!) shard, int n_blocks, int block_len, "
+      "int g_stride, int g_off, int dist, float p0, float p1, "
+      "int[] tail_ops, float[] tail_s0, float[] tail_s1, int full_numel, "
+      "*, int seed, int offset) -> Tensor(a!)");
 }
 
 TORCH_LIBRARY_IMPL(tdx, CPU, m) {
@@ -359,6 +473,8 @@ TORCH_LIBRARY_IMPL(tdx, CPU, m) {
   m.impl("uniform_shard_win_", cpu_uniform_shard_win_);
   m.impl("normal_shard_win_", cpu_normal_shard_win_);
   m.impl("bernoulli_shard_win_", cpu_bernoulli_shard_win_);
+  m.impl("rng_chain_", cpu_rng_chain_);
+  m.impl("rng_chain_shard_win_", cpu_rng_chain_shard_win_);
 }
 
 }  // namespace

@@ -715,6 +715,386 @@ at::Tensor& tdx_bernoulli_shard_win_(at::Tensor& shard, int64_t n_blocks,
   return shard;
 }
 
+// ---------------------------------------------------------------------------
+// Fused init chains: an RNG value step followed by a recorded tail of
+// pointwise-scalar ops (trunc_normal_ is uniform_ -> erfinv_ -> mul_ ->
+// add_ -> clamp_) in ONE kernel. Unfused, every tail op is an ATen kernel
+// that reads and writes the whole tensor; here the tail runs on the
+// values in registers before the single store. The result is bitwise
+// what the separate kernels give (applyTail below spells out why).
+// ---------------------------------------------------------------------------
+
+constexpr int kMaxTail = 8;
+
+// Opcodes: TailOp::Code in csrc/core/deferred_init.h.
+enum TailCode : int32_t {
+  kTailErfinv = 0,
+  kTailMul = 1,
+  kTailAdd = 2,
+  kTailSub = 3,
+  kTailClamp = 4,
+  kTailClampMin = 5,
+  kTailClampMax = 6,
+  kTailNeg = 7,
+  kTailAbs = 8,
+};
+
+struct TailStep {
+  int32_t op;
+  float s0;
+  float s1;
+};
+
+// Passed by value as a kernel argument (or read from the batched blob):
+// uniform across the grid, so the opcode switch is a scalar branch.
+struct TailProgram {
+  // f16 tensors only: elements of the full tensor from this index on get
+  // their mul results rounded once (tailMul below).
+  uint64_t once_from;
+  int32_t n;
+  TailStep steps[kMaxTail];
+};
+
+// ATen's vectorized elementwise kernel works in blocks of this many
+// elements for 2-byte dtypes on ROCm (256 threads x 8); the block that
+// holds the last numel % kAtenBlock16 elements takes another code path.
+constexpr int64_t kAtenBlock16 = 2048;
+
+// What ATen leaves in memory between two kernels: the value rounded to T.
+template <typename T>
+__device__ __forceinline__ float roundThrough(float v) {
+  if constexpr (std::is_same_v<T, __hip_bfloat16>) {
+    return __bfloat162float(from_float<T>(v));
+  } else if constexpr (std::is_same_v<T, __half>) {
+    return __half2float(from_float<T>(v));
+  } else {
+    return from_float<T>(v);
+  }
+}
+
+// A tensor element times a float immediate, rounded the way ATen's kernel
+// rounds it. That is the float product followed by the store's rounding
+// to T — except on f16 tensors in ATen's last, partial block, whose
+// multiply-and-narrow compiles to a mixed-precision FMA that rounds the
+// exact product to f16 ONCE (measured on gfx950: every element of the
+// last numel % 2048, and no other, equals the once-rounded product;
+// add/sub round twice everywhere, and bf16 has no such instruction).
+// The f16 x f32 product is exact in double, and double -> f16 rounds
+// once.
+template <typename T>
+__device__ __forceinline__ float tailMul(float v, float s, bool once) {
+  if constexpr (std::is_same_v<T, __half>) {
+    if (once) {
+      const double r = static_cast<double>(v) * static_cast<double>(s);
+      return static_cast<float>(static_cast<_Float16>(r));
+    }
+  }
+  return __fmul_rn(v, s);
+}
+
+// Applies the tail to one group's values, reproducing the bits of the
+// separate ATen kernels:
+//  * the value is rounded to T after the RNG step and after every tail
+//    step (ATen stores T between kernels), and each step computes in
+//    float on the widened value (ATen's opmath_t);
+//  * contraction is off in this function: hipcc would otherwise turn
+//    mul -> add on an f32 tensor into one FMA, which ATen cannot do
+//    across kernels;
+//  * clamp keeps NaN and otherwise takes min(max(v, lo), hi), ATen's
+//    scalar clamp order;
+//  * erfinv is the device library's erfinvf on the widened value.
+//  * mul on f16 tensors follows ATen's position-dependent rounding
+//    (tailMul); `elem0` is the index of vals[0] in the full tensor.
+// Measured on gfx950 this matches ATen on every element except for
+// erfinv on f32 tensors, which the planner therefore admits only on
+// explicit request (tailOpAdmitted in csrc/core/deferred_init.cc):
+// ATen's f32 kernel is 1-2 ulp away on about half of all inputs, and an
+// f64 erfinv would cost scratch and half the occupancy.
+template <typename T, int kElems>
+__device__ __forceinline__ void applyTail(float (&vals)[kElems],
+                                          const TailProgram& prog,
+                                          uint64_t elem0) {
+#pragma clang fp contract(off)
+  const uint64_t once_from = prog.once_from;
+#pragma unroll
+  for (int j = 0; j < kElems; ++j) {
+    vals[j] = roundThrough<T>(vals[j]);
+  }
+  for (int s = 0; s < prog.n; ++s) {
+    const int32_t op = prog.steps[s].op;
+    const float s0 = prog.steps[s].s0;
+    const float s1 = prog.steps[s].s1;
+    switch (op) {
+      case kTailErfinv:
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) {
+          vals[j] = roundThrough<T>(erfinvf(vals[j]));
+        }
+        break;
+      case kTailMul:
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) {
+          vals[j] = roundThrough<T>(
+              tailMul<T>(vals[j], s0, elem0 + j >= once_from));
+        }
+        break;
+      case kTailAdd:
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) {
+          vals[j] = roundThrough<T>(__fadd_rn(vals[j], s0));
+        }
+        break;
+      case kTailSub:
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) {
+          vals[j] = roundThrough<T>(__fsub_rn(vals[j], s0));
+        }
+        break;
+      case kTailClamp:
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) {
+          const float v = vals[j];
+          vals[j] = roundThrough<T>(v != v ? v : fminf(fmaxf(v, s0), s1));
+        }
+        break;
+      case kTailClampMin:
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) {
+          const float v = vals[j];
+          vals[j] = roundThrough<T>(v != v ? v : fmaxf(v, s0));
+        }
+        break;
+      case kTailClampMax:
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) {
+          const float v = vals[j];
+          vals[j] = roundThrough<T>(v != v ? v : fminf(v, s0));
+        }
+        break;
+      case kTailNeg:
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) {
+          vals[j] = roundThrough<T>(-vals[j]);
+        }
+        break;
+      default:  // kTailAbs; the host validates opcodes
+#pragma unroll
+        for (int j = 0; j < kElems; ++j) {
+          vals[j] = roundThrough<T>(fabsf(vals[j]));
+        }
+        break;
+    }
+  }
+}
+
+// rng_shard_window_kernel with the tail applied before the store. Same
+// window geometry and index-width rule. The group-indexed vector path
+// additionally serves a single block (n_blocks == 1, the whole-tensor and
+// flat dim-0 case) whose length is not a group multiple: its one partial
+// last group is stored elementwise by one thread. `vec_ok` is the host's
+// check that `out` is 16-byte aligned.
+template <typename T, Dist kDist, typename IdxT>
+__global__ void rng_chain_window_kernel(T* __restrict__ out,
+                                        IdxT n_blocks,
+                                        IdxT block_len,
+                                        int64_t g_stride,
+                                        int64_t g_off,
+                                        bool vec_ok,
+                                        float a,
+                                        float b,
+                                        uint64_t seed,
+                                        uint64_t offset,
+                                        TailProgram prog) {
+  constexpr int kElems = VecTraits<T>::kElems;
+  using Vec = typename VecTraits<T>::Vec;
+  const IdxT stride = static_cast<IdxT>(gridDim.x) * blockDim.x;
+  const bool vec_aligned =
+      vec_ok && (g_off % kElems) == 0 &&
+      (n_blocks == 1 ||
+       ((block_len % kElems) == 0 && (g_stride % kElems) == 0));
+  if (vec_aligned) {
+    const IdxT gpb = block_len / kElems;  // full groups per window block
+    const IdxT n_groups = n_blocks * gpb;
+    const uint64_t g0 = static_cast<uint64_t>(g_off) / kElems;
+    const uint64_t gs = static_cast<uint64_t>(g_stride) / kElems;
+    for (IdxT j = blockIdx.x * static_cast<IdxT>(blockDim.x) + threadIdx.x;
+         j < n_groups; j += stride) {
+      const IdxT blk = j / gpb;
+      const IdxT within = j - blk * gpb;
+      const uint64_t g = g0 + static_cast<uint64_t>(blk) * gs + within;
+      float vals[kElems];
+      rngGroupValues<T, kDist>(g, a, b, seed, offset, vals);
+      applyTail<T, kElems>(vals, prog, g * kElems);
+      Vec v;
+      T* vp = reinterpret_cast<T*>(&v);
+#pragma unroll
+      for (int e = 0; e < kElems; ++e) {
+        vp[e] = from_float<T>(vals[e]);
+      }
+      *reinterpret_cast<Vec*>(out + static_cast<uint64_t>(j) * kElems) = v;
+    }
+    // Only a single block can have a partial last group here.
+    const uint32_t tail_elems =
+        static_cast<uint32_t>(block_len - gpb * kElems);
+    if (tail_elems != 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+      float vals[kElems];
+      rngGroupValues<T, kDist>(g0 + gpb, a, b, seed, offset, vals);
+      applyTail<T, kElems>(vals, prog, (g0 + gpb) * kElems);
+      for (uint32_t e = 0; e < tail_elems; ++e) {
+        out[static_cast<uint64_t>(gpb) * kElems + e] = from_float<T>(vals[e]);
+      }
+    }
+    return;
+  }
+  const IdxT n = n_blocks * block_len;
+  for (IdxT i = blockIdx.x * static_cast<IdxT>(blockDim.x) + threadIdx.x;
+       i < n; i += stride) {
+    const IdxT blk = i / block_len;
+    const IdxT rem = i - blk * block_len;
+    const uint64_t ge = static_cast<uint64_t>(g_off) +
+                        static_cast<uint64_t>(blk) * g_stride + rem;
+    const uint64_t g = ge / kElems;
+    float vals[kElems];
+    rngGroupValues<T, kDist>(g, a, b, seed, offset, vals);
+    applyTail<T, kElems>(vals, prog, g * kElems);
+    out[i] = from_float<T>(vals[ge - g * kElems]);
+  }
+}
+
+// `full_numel` is the element count of the FULL tensor the values belong
+// to (a shard passes its parent's): it places ATen's last, partial block.
+TailProgram makeTailProgram(at::IntArrayRef tail_ops,
+                            at::ArrayRef<double> tail_s0,
+                            at::ArrayRef<double> tail_s1,
+                            int64_t full_numel) {
+  TORCH_CHECK(tail_ops.size() <= static_cast<size_t>(kMaxTail) &&
+                  tail_s0.size() == tail_ops.size() &&
+                  tail_s1.size() == tail_ops.size(),
+              "rng_chain: at most ", kMaxTail,
+              " tail ops, with one s0 and one s1 each");
+  TORCH_CHECK(full_numel >= 0, "rng_chain: full_numel must be >= 0");
+  TailProgram prog{};
+  prog.once_from =
+      static_cast<uint64_t>(full_numel / kAtenBlock16 * kAtenBlock16);
+  prog.n = static_cast<int32_t>(tail_ops.size());
+  for (size_t i = 0; i < tail_ops.size(); ++i) {
+    TORCH_CHECK(kTailErfinv <= tail_ops[i] && tail_ops[i] <= kTailAbs,
+                "rng_chain: bad tail opcode ", tail_ops[i]);
+    prog.steps[i].op = static_cast<int32_t>(tail_ops[i]);
+    // double -> float, the way ATen narrows a scalar operand to opmath_t.
+    prog.steps[i].s0 = static_cast<float>(tail_s0[i]);
+    prog.steps[i].s1 = static_cast<float>(tail_s1[i]);
+  }
+  return prog;
+}
+
+template <Dist kDist>
+void launchRngChainWindow(at::Tensor& shard, int64_t n_blocks,
+                          int64_t block_len, int64_t g_stride, int64_t g_off,
+                          double p0, double p1, const TailProgram& prog,
+                          int64_t seed, int64_t offset) {
+  TORCH_CHECK(shard.is_contiguous(),
+              "tdx shard kernels require contiguous tensors");
+  TORCH_CHECK(n_blocks >= 0 && block_len >= 0 && g_stride >= block_len &&
+                  g_off >= 0,
+              "invalid shard window");
+  TORCH_CHECK(shard.numel() == n_blocks * block_len,
+              "shard numel must equal n_blocks * block_len");
+  if (shard.numel() == 0) {
+    return;
+  }
+  float a = static_cast<float>(p0);
+  float b = kDist == Dist::kUniform ? static_cast<float>(p1 - p0)
+                                    : static_cast<float>(p1);
+  const bool vec_ok =
+      reinterpret_cast<uintptr_t>(shard.data_ptr()) % 16 == 0;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  auto launch = [&](auto type_tag) {
+    using T = decltype(type_tag);
+    const int64_t n_work =
+        (shard.numel() + VecTraits<T>::kElems - 1) / VecTraits<T>::kElems;
+    auto launch_idx = [&](auto idx_tag) {
+      using IdxT = decltype(idx_tag);
+      hipLaunchKernelGGL((rng_chain_window_kernel<T, kDist, IdxT>),
+                         dim3(numBlocks(n_work)), dim3(kBlock), 0,
+                         stream.stream(),
+                         reinterpret_cast<T*>(shard.data_ptr()),
+                         static_cast<IdxT>(n_blocks),
+                         static_cast<IdxT>(block_len), g_stride, g_off,
+                         vec_ok, a, b, static_cast<uint64_t>(seed),
+                         static_cast<uint64_t>(offset), prog);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
+    };
+    if (shard.numel() <= std::numeric_limits<int32_t>::max()) {
+      launch_idx(uint32_t{});
+    } else {
+      launch_idx(int64_t{});
+    }
+  };
+  switch (shard.scalar_type()) {
+    case at::kFloat:
+      launch(float{});
+      break;
+    case at::kBFloat16:
+      launch(__hip_bfloat16{});
+      break;
+    case at::kHalf:
+      launch(__half{});
+      break;
+    default:
+      TORCH_CHECK(false, "tdx chain kernels support float32/bf16/fp16, got ",
+                  shard.scalar_type());
+  }
+}
+
+at::Tensor& tdx_rng_chain_shard_win_(
+    at::Tensor& shard, int64_t n_blocks, int64_t block_len, int64_t g_stride,
+    int64_t g_off, int64_t dist, double p0, double p1,
+    at::IntArrayRef tail_ops, at::ArrayRef<double> tail_s0,
+    at::ArrayRef<double> tail_s1, int64_t full_numel, int64_t seed,
+    int64_t offset) {
+  TORCH_CHECK(full_numel >= g_off + (n_blocks > 0 ? (n_blocks - 1) * g_stride
+                                                  + block_len : 0),
+              "rng_chain: the window does not fit in full_numel");
+  const TailProgram prog =
+      makeTailProgram(tail_ops, tail_s0, tail_s1, full_numel);
+  switch (dist) {
+    case 0:
+      launchRngChainWindow<Dist::kUniform>(shard, n_blocks, block_len,
+                                           g_stride, g_off, p0, p1, prog,
+                                           seed, offset);
+      break;
+    case 1:
+      TORCH_CHECK(p1 >= 0.0, "normal_ expects std >= 0.0, but found std=",
+                  p1);
+      launchRngChainWindow<Dist::kNormal>(shard, n_blocks, block_len,
+                                          g_stride, g_off, p0, p1, prog,
+                                          seed, offset);
+      break;
+    case 2:
+      TORCH_CHECK(0.0 <= p0 && p0 <= 1.0,
+                  "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
+      launchRngChainWindow<Dist::kBernoulli>(shard, n_blocks, block_len,
+                                             g_stride, g_off, p0, 0.0, prog,
+                                             seed, offset);
+      break;
+    default:
+      TORCH_CHECK(false, "rng_chain: dist must be 0 (uniform), 1 (normal) "
+                         "or 2 (bernoulli), got ", dist);
+  }
+  return shard;
+}
+
+at::Tensor& tdx_rng_chain_(at::Tensor& self, int64_t dist, double p0,
+                           double p1, at::IntArrayRef tail_ops,
+                           at::ArrayRef<double> tail_s0,
+                           at::ArrayRef<double> tail_s1, int64_t seed,
+                           int64_t offset) {
+  return tdx_rng_chain_shard_win_(self, 1, self.numel(), self.numel(), 0,
+                                  dist, p0, p1, tail_ops, tail_s0, tail_s1,
+                                  self.numel(), seed, offset);
+}
+
 at::Tensor& tdx_fill_(at::Tensor& self, const at::Scalar& value) {
   TORCH_CHECK(self.is_contiguous(),
               "tdx init kernels require contiguous tensors");
@@ -899,12 +1279,16 @@ struct InitTensorMeta {
   uint64_t seed, offset;
 };
 
-template <typename T, Dist kDist>
+// kHasTail: apply the tensor's fused pointwise tail (`tail`, in the blob)
+// before the stores; the false instantiation is the tail-free code as it
+// always was.
+template <typename T, Dist kDist, bool kHasTail>
 __device__ __forceinline__ void fillRangeVec(T* __restrict__ out,
                                              int64_t begin, int64_t end,
                                              int64_t n, float a, float b,
                                              uint64_t seed,
-                                             uint64_t offset) {
+                                             uint64_t offset,
+                                             const TailProgram* tail) {
   constexpr int kElems = VecTraits<T>::kElems;
   using Vec = typename VecTraits<T>::Vec;
   // begin is kInitEPB-aligned (hence kElems-aligned); only the last
@@ -916,6 +1300,9 @@ __device__ __forceinline__ void fillRangeVec(T* __restrict__ out,
     float vals[kElems];
     rngGroupValues<T, kDist>(static_cast<uint64_t>(base / kElems), a, b,
                              seed, offset, vals);
+    if constexpr (kHasTail) {
+      applyTail<T, kElems>(vals, *tail, static_cast<uint64_t>(base));
+    }
     Vec v;
     T* vp = reinterpret_cast<T*>(&v);
 #pragma unroll
@@ -928,6 +1315,9 @@ __device__ __forceinline__ void fillRangeVec(T* __restrict__ out,
     float vals[kElems];
     rngGroupValues<T, kDist>(static_cast<uint64_t>(full_end / kElems), a,
                              b, seed, offset, vals);
+    if constexpr (kHasTail) {
+      applyTail<T, kElems>(vals, *tail, static_cast<uint64_t>(full_end));
+    }
     for (int64_t e = full_end; e < end; ++e) {
       out[e] = from_float<T>(vals[e - full_end]);
     }
@@ -959,23 +1349,24 @@ __device__ __forceinline__ void fillRangeConst(T* __restrict__ out,
   }
 }
 
-template <typename T>
+template <typename T, bool kHasTail>
 __device__ __forceinline__ void initDispatchDist(const InitTensorMeta& mt,
                                                  int64_t begin,
-                                                 int64_t end) {
+                                                 int64_t end,
+                                                 const TailProgram* tail) {
   T* out = static_cast<T*>(mt.ptr);
   switch (mt.dist) {
     case 0:
-      fillRangeVec<T, Dist::kUniform>(out, begin, end, mt.n, mt.a, mt.b,
-                                      mt.seed, mt.offset);
+      fillRangeVec<T, Dist::kUniform, kHasTail>(out, begin, end, mt.n, mt.a, mt.b,
+                                      mt.seed, mt.offset, tail);
       break;
     case 1:
-      fillRangeVec<T, Dist::kNormal>(out, begin, end, mt.n, mt.a, mt.b,
-                                     mt.seed, mt.offset);
+      fillRangeVec<T, Dist::kNormal, kHasTail>(out, begin, end, mt.n, mt.a, mt.b,
+                                     mt.seed, mt.offset, tail);
       break;
     case 2:
-      fillRangeVec<T, Dist::kBernoulli>(out, begin, end, mt.n, mt.a, mt.b,
-                                        mt.seed, mt.offset);
+      fillRangeVec<T, Dist::kBernoulli, kHasTail>(out, begin, end, mt.n, mt.a, mt.b,
+                                        mt.seed, mt.offset, tail);
       break;
     case 3:
       fillRangeConst<T>(out, begin, end, mt.n, mt.a);
@@ -986,13 +1377,23 @@ __device__ __forceinline__ void initDispatchDist(const InitTensorMeta& mt,
   }
 }
 
-// blob layout: int64 prefix[n_tensors] then InitTensorMeta[n_tensors].
+// blob layout: int64 prefix[n_tensors], InitTensorMeta[n_tensors] and,
+// when kHasTail, TailProgram[n_tensors] (n == 0 for a tensor without a
+// tail). The tails sit in a table of their own, not in InitTensorMeta,
+// so a batch without tails reads the blob it always read and launches
+// the instantiation that compiles to the code that was here before.
+template <bool kHasTail>
 __global__ void batched_init_kernel(const uint8_t* __restrict__ blob,
                                     int32_t n_tensors,
                                     int64_t total_vblocks) {
   const int64_t* prefix = reinterpret_cast<const int64_t*>(blob);
   const InitTensorMeta* metas = reinterpret_cast<const InitTensorMeta*>(
       blob + sizeof(int64_t) * n_tensors);
+  const TailProgram* tails =
+      kHasTail ? reinterpret_cast<const TailProgram*>(
+                     blob + (sizeof(int64_t) + sizeof(InitTensorMeta)) *
+                                n_tensors)
+               : nullptr;
 
   for (int64_t vb = blockIdx.x; vb < total_vblocks; vb += gridDim.x) {
     int lo = 0, hi = n_tensors - 1;
@@ -1007,15 +1408,16 @@ __global__ void batched_init_kernel(const uint8_t* __restrict__ blob,
     const InitTensorMeta mt = metas[lo];
     const int64_t begin = (vb - prefix[lo]) * kInitEPB;
     const int64_t end = begin + kInitEPB < mt.n ? begin + kInitEPB : mt.n;
+    const TailProgram* tail = kHasTail ? tails + lo : nullptr;
     switch (mt.dtype) {
       case 0:
-        initDispatchDist<float>(mt, begin, end);
+        initDispatchDist<float, kHasTail>(mt, begin, end, tail);
         break;
       case 1:
-        initDispatchDist<__hip_bfloat16>(mt, begin, end);
+        initDispatchDist<__hip_bfloat16, kHasTail>(mt, begin, end, tail);
         break;
       default:
-        initDispatchDist<__half>(mt, begin, end);
+        initDispatchDist<__half, kHasTail>(mt, begin, end, tail);
         break;
     }
   }
@@ -1028,16 +1430,33 @@ void batched_init_launch(std::vector<at::Tensor> tensors,
                          std::vector<double> p0s,
                          std::vector<double> p1s,
                          std::vector<int64_t> seeds,
-                         std::vector<int64_t> offsets) {
+                         std::vector<int64_t> offsets,
+                         std::vector<std::vector<int64_t>> tail_ops,
+                         std::vector<std::vector<double>> tail_s0,
+                         std::vector<std::vector<double>> tail_s1) {
   const size_t n_tensors = tensors.size();
   TORCH_CHECK(n_tensors > 0 && dists.size() == n_tensors &&
                   p0s.size() == n_tensors && p1s.size() == n_tensors &&
                   seeds.size() == n_tensors && offsets.size() == n_tensors,
               "batched init: list length mismatch");
+  // The tail lists are optional as a whole (old call sites pass none).
+  TORCH_CHECK((tail_ops.empty() && tail_s0.empty() && tail_s1.empty()) ||
+                  (tail_ops.size() == n_tensors &&
+                   tail_s0.size() == n_tensors &&
+                   tail_s1.size() == n_tensors),
+              "batched init: tail list length mismatch");
+  bool has_tail = false;
+  for (const auto& ops : tail_ops) {
+    has_tail = has_tail || !ops.empty();
+  }
 
   const size_t prefix_bytes = sizeof(int64_t) * n_tensors;
+  static_assert(sizeof(InitTensorMeta) % alignof(TailProgram) == 0 &&
+                    sizeof(int64_t) % alignof(TailProgram) == 0,
+                "the tail table must stay aligned behind the metas");
+  const size_t tails_off = prefix_bytes + sizeof(InitTensorMeta) * n_tensors;
   const size_t blob_bytes =
-      prefix_bytes + sizeof(InitTensorMeta) * n_tensors;
+      tails_off + (has_tail ? sizeof(TailProgram) * n_tensors : 0);
   at::Tensor host_blob = at::empty(
       {static_cast<int64_t>(blob_bytes)},
       at::TensorOptions().dtype(at::kByte).pinned_memory(true));
@@ -1077,6 +1496,13 @@ void batched_init_launch(std::vector<at::Tensor> tensors,
                         : static_cast<float>(p1);
     mt.seed = static_cast<uint64_t>(seeds[t]);
     mt.offset = static_cast<uint64_t>(offsets[t]);
+    if (has_tail) {
+      TORCH_CHECK(tail_ops[t].empty() || mt.dist <= 2,
+                  "batched init: only RNG plans carry a tail");
+      reinterpret_cast<TailProgram*>(
+          static_cast<uint8_t*>(host_blob.data_ptr()) + tails_off)[t] =
+          makeTailProgram(tail_ops[t], tail_s0[t], tail_s1[t], mt.n);
+    }
     prefix[t] = total_vblocks;
     total_vblocks += (mt.n + kInitEPB - 1) / kInitEPB;
   }
@@ -1086,10 +1512,17 @@ void batched_init_launch(std::vector<at::Tensor> tensors,
   const int grid =
       static_cast<int>(std::min<int64_t>(total_vblocks, 16384));
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(batched_init_kernel, dim3(grid), dim3(kBlock), 0,
-                     stream.stream(),
-                     static_cast<const uint8_t*>(dev_blob.const_data_ptr()),
-                     static_cast<int32_t>(n_tensors), total_vblocks);
+  if (has_tail) {
+    hipLaunchKernelGGL(batched_init_kernel<true>, dim3(grid), dim3(kBlock), 0,
+                       stream.stream(),
+                       static_cast<const uint8_t*>(dev_blob.const_data_ptr()),
+                       static_cast<int32_t>(n_tensors), total_vblocks);
+  } else {
+    hipLaunchKernelGGL(batched_init_kernel<false>, dim3(grid), dim3(kBlock),
+                       0, stream.stream(),
+                       static_cast<const uint8_t*>(dev_blob.const_data_ptr()),
+                       static_cast<int32_t>(n_tensors), total_vblocks);
+  }
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -1110,6 +1543,8 @@ TORCH_LIBRARY_IMPL(tdx, CUDA, m) {
   m.impl("uniform_shard_win_", tdx_uniform_shard_win_);
   m.impl("normal_shard_win_", tdx_normal_shard_win_);
   m.impl("bernoulli_shard_win_", tdx_bernoulli_shard_win_);
+  m.impl("rng_chain_", tdx_rng_chain_);
+  m.impl("rng_chain_shard_win_", tdx_rng_chain_shard_win_);
 }
 
 }  // namespace

@@ -25,7 +25,10 @@ void batched_init_launch(std::vector<at::Tensor> tensors,
                          std::vector<double> p0s,
                          std::vector<double> p1s,
                          std::vector<int64_t> seeds,
-                         std::vector<int64_t> offsets);
+                         std::vector<int64_t> offsets,
+                         std::vector<std::vector<int64_t>> tail_ops,
+                         std::vector<std::vector<double>> tail_s0,
+                         std::vector<std::vector<double>> tail_s1);
 
 void anyprecision_adamw_batched_step(
     std::vector<at::Tensor> params,
@@ -50,14 +53,21 @@ PYBIND11_MODULE(_K, m) {
   m.def("has_anyprecision_adamw", [] { return true; });
   m.def("has_anyprecision_adamw_batched", [] { return true; });
   m.def("has_batched_init", [] { return true; });
+  m.def("has_fused_chains", [] { return true; });
 
   m.def("batched_init_", &tdx::batched_init_launch,
         pybind11::arg("tensors"), pybind11::arg("dists"),
         pybind11::arg("p0s"), pybind11::arg("p1s"), pybind11::arg("seeds"),
         pybind11::arg("offsets"),
+        pybind11::arg("tail_ops") = std::vector<std::vector<int64_t>>{},
+        pybind11::arg("tail_s0") = std::vector<std::vector<double>>{},
+        pybind11::arg("tail_s1") = std::vector<std::vector<double>>{},
         "One launch filling every listed tensor with its reduced init "
         "plan (dist: 0 uniform, 1 normal, 2 bernoulli, 3 fill, 4 zero); "
-        "bitwise-identical to the per-tensor tdx kernels.");
+        "bitwise-identical to the per-tensor tdx kernels. The optional "
+        "tail lists give each tensor's fused pointwise tail (opcodes and "
+        "scalars as in tdx::rng_chain_; empty for none), applied in "
+        "registers before the store.");
 
   m.def("anyprecision_adamw_batched_",
         &tdx::anyprecision_adamw_batched_step, pybind11::arg("params"),

@@ -158,6 +158,11 @@ def materialize_module(
 _DIST_CODE = {"uniform": 0, "normal": 1, "bernoulli": 2, "fill": 3,
               "zero": 4, "factory": -1}
 
+# Tail opcodes of the fused chain kernels (TailOp::Code in
+# csrc/core/deferred_init.h), keyed by the names tensor_chain_plan reports.
+_TAIL_CODE = {"erfinv": 0, "mul": 1, "add": 2, "sub": 3, "clamp": 4,
+              "clamp_min": 5, "clamp_max": 6, "neg": 7, "abs": 8}
+
 
 def materialize_module_batched(
     module: Module,
@@ -169,8 +174,13 @@ def materialize_module_batched(
     parameter/buffer whose tape is a simple init chain collapses to its
     final whole-tensor value step, and ALL of them fill in ONE CDNA4
     kernel launch (bitwise-identical to the per-tensor replay — each
-    tensor keeps its pinned Philox stream). Tensors with richer tapes
-    (views, cross-tensor dependencies, pointwise tails) fall back to
+    tensor keeps its pinned Philox stream). An RNG step followed by a
+    fusable pointwise-scalar tail (``trunc_normal_``'s ``uniform_ ->
+    erfinv_ -> mul_ -> add_ -> clamp_``) is part of that launch: the
+    kernel applies the tail in registers before the store. Tensors with
+    richer tapes (views, cross-tensor dependencies, tails outside the
+    fusable set such as ``div_`` or ``add_(alpha != 1)``, any tail while
+    ``_C.set_fused_init_chains(False)`` is in effect) fall back to
     ordinary replay. GPU-only; CPU targets use :func:`materialize_module`.
 
     Launch count for a Llama-3-70B replica drops from ~560 to ~3.
@@ -180,7 +190,8 @@ def materialize_module_batched(
     lands straight in HBM; the pinned counters make uniform/bernoulli/
     fill bits identical across devices, normals equivalent but
     per-device-transformed). Fallback tensors replay on their recorded
-    device and are then moved."""
+    device and are then moved; a chain with a pointwise tail recorded on
+    another device is one of them (erfinv bits are per device)."""
     import torch
 
     from torchdistx_amd import _kernels
@@ -210,6 +221,14 @@ def materialize_module_batched(
             submodule._buffers[key] = mat
 
 
+def _same_device(a, b) -> bool:
+    """Device equality where a missing index matches any ("cuda" is
+    "cuda:0" for this purpose)."""
+    return a.type == b.type and (
+        a.index is None or b.index is None or a.index == b.index
+    )
+
+
 def _batched_fill(entries, device=None) -> list:
     """Fills every plannable (simple-chain, GPU, f32/bf16/f16) entry with
     one batched kernel launch and swaps the module slots; returns the
@@ -237,8 +256,12 @@ def _batched_fill(entries, device=None) -> list:
     if not gpu:
         return list(entries)
 
+    fused = (
+        hasattr(_kernels._K, "has_fused_chains")
+        and _kernels._K.has_fused_chains()
+    )
     batch = {"t": [], "dist": [], "p0": [], "p1": [], "seed": [],
-             "offset": [], "entry": []}
+             "offset": [], "tail": [], "entry": []}
     fallback = []
     seen = {}  # id(fake) -> out: tied params must share ONE allocation
     for entry in entries:
@@ -246,7 +269,11 @@ def _batched_fill(entries, device=None) -> list:
         if id(tensor) in seen:
             batch["entry"].append((entry, seen[id(tensor)]))
             continue
-        plan = _C.tensor_init_plan(tensor)
+        if fused:
+            plan = _C.tensor_chain_plan(tensor)
+        else:
+            plan = _C.tensor_init_plan(tensor)
+        tail = plan.get("tail", []) if plan is not None else []
         if (
             plan is None
             or plan["dtype"] not in (
@@ -255,6 +282,13 @@ def _batched_fill(entries, device=None) -> list:
             # One batched launch targets one device; stray tensors of a
             # mixed-device module replay normally.
             or (device is None and plan["device"] != entries[0][2].device)
+            # A tail recorded on another device replays there: the
+            # uniform bits match across devices, erfinv's need not.
+            or (
+                tail
+                and device is not None
+                and not _same_device(plan["device"], device)
+            )
         ):
             fallback.append(entry)
             continue
@@ -272,10 +306,19 @@ def _batched_fill(entries, device=None) -> list:
             batch["p1"].append(plan["p1"])
             batch["seed"].append(plan["seed"])
             batch["offset"].append(plan["offset"])
+            batch["tail"].append(tail)
         # kind == "factory": allocate-only, matching aten::empty replay.
         batch["entry"].append((entry, out))
 
-    if batch["t"]:
+    if batch["t"] and any(batch["tail"]):
+        _kernels._K.batched_init_(
+            batch["t"], batch["dist"], batch["p0"], batch["p1"],
+            batch["seed"], batch["offset"],
+            [[_TAIL_CODE[name] for name, _, _ in t] for t in batch["tail"]],
+            [[s0 for _, s0, _ in t] for t in batch["tail"]],
+            [[s1 for _, _, s1 in t] for t in batch["tail"]],
+        )
+    elif batch["t"]:
         _kernels._K.batched_init_(
             batch["t"], batch["dist"], batch["p0"], batch["p1"],
             batch["seed"], batch["offset"],
