@@ -9,6 +9,7 @@ def has_anyprecision_adamw() -> bool: ...
 def has_anyprecision_adamw_batched() -> bool: ...
 def has_batched_init() -> bool: ...
 def has_fused_chains() -> bool: ...
+def has_box_kernel() -> bool: ...
 def anyprecision_adamw_(
     param: torch.Tensor,
     grad: torch.Tensor,

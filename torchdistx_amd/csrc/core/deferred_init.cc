@@ -41,6 +41,7 @@
 #include <c10/core/impl/LocalDispatchKeySet.h>
 #include <torch/library.h>
 
+#include "box_geometry.h"
 #include "fake.h"
 #include "native_redirect.h"
 #include "stack_utils.h"
@@ -1396,10 +1397,47 @@ struct ShardWindow {
   int64_t block_len;
   int64_t g_stride;
   int64_t g_off;
+  // Set for an N-d box of two or more levels (materializeTensorBlock),
+  // which takes tdx::rng_box_; the four fields above are then unused.
+  std::optional<BoxGeometry> box = std::nullopt;
 };
 
+int64_t rngDistCode(ChainStep::Kind kind) {
+  return kind == ChainStep::Kind::kUniform
+             ? 0
+             : (kind == ChainStep::Kind::kNormal ? 1 : 2);
+}
+
+// One tdx::rng_box_ launch: the RNG step over the box, with `tail` (may
+// be empty) applied before the store.
+void applyBoxStep(const ChainStep& rng, const std::vector<TailOp>& tail,
+                  at::Tensor& shard, const BoxGeometry& box,
+                  int64_t full_numel) {
+  static const auto rng_box =
+      c10::Dispatcher::singleton()
+          .findSchemaOrThrow("tdx::rng_box_", "")
+          .typed<at::Tensor&(at::Tensor&, at::IntArrayRef, at::IntArrayRef,
+                             int64_t, int64_t, int64_t, double, double,
+                             at::IntArrayRef, at::ArrayRef<double>,
+                             at::ArrayRef<double>, int64_t, int64_t,
+                             int64_t)>();
+  std::vector<int64_t> ops;
+  std::vector<double> s0;
+  std::vector<double> s1;
+  for (const TailOp& t : tail) {
+    ops.push_back(t.op);
+    s0.push_back(t.s0);
+    s1.push_back(t.s1);
+  }
+  rng_box.call(shard, at::IntArrayRef(box.extent, box.levels),
+               at::IntArrayRef(box.g_stride, box.levels), box.run_len,
+               box.g_off, rngDistCode(rng.kind), rng.p0, rng.p1, ops, s0, s1,
+               full_numel, static_cast<int64_t>(rng.philox->first),
+               static_cast<int64_t>(rng.philox->second));
+}
+
 void applyShardStep(const ChainStep& step, at::Tensor& shard,
-                    const ShardWindow& w) {
+                    const ShardWindow& w, int64_t full_numel) {
   switch (step.kind) {
     case ChainStep::Kind::kFactory:
     case ChainStep::Kind::kPass:
@@ -1428,6 +1466,10 @@ void applyShardStep(const ChainStep& step, at::Tensor& shard,
       TORCH_CHECK(step.philox.has_value(),
                   "slice materialization: this RNG op carries no pinned "
                   "Philox state (was it recorded by an older build?)");
+      if (w.box.has_value()) {
+        applyBoxStep(step, {}, shard, *w.box, full_numel);
+        return;
+      }
       static const auto uniform_shard =
           c10::Dispatcher::singleton()
               .findSchemaOrThrow("tdx::uniform_shard_", "")
@@ -1488,20 +1530,19 @@ void applyShardStep(const ChainStep& step, at::Tensor& shard,
   }
 }
 
-int64_t rngDistCode(ChainStep::Kind kind) {
-  return kind == ChainStep::Kind::kUniform
-             ? 0
-             : (kind == ChainStep::Kind::kNormal ? 1 : 2);
-}
-
 // One launch for an RNG step and the fusable tail after it: the window
-// op draws the values and applies the tail before its single store.
+// (or box) op draws the values and applies the tail before its single
+// store.
 void applyFusedShardStep(const ChainStep& rng, const std::vector<TailOp>& tail,
                          at::Tensor& shard, const ShardWindow& w,
                          int64_t full_numel) {
   TORCH_CHECK(rng.philox.has_value(),
               "slice materialization: this RNG op carries no pinned "
               "Philox state (was it recorded by an older build?)");
+  if (w.box.has_value()) {
+    applyBoxStep(rng, tail, shard, *w.box, full_numel);
+    return;
+  }
   static const auto chain_shard_win =
       c10::Dispatcher::singleton()
           .findSchemaOrThrow("tdx::rng_chain_shard_win_", "")
@@ -1673,6 +1714,51 @@ std::optional<ChainPlan> chainPlanImpl(const at::Tensor& tensor,
   return plan;
 }
 
+// Allocates the shard and applies the tensor's init chain to it over the
+// window (or box) `w` of the full tensor.
+at::Tensor replayChainOnShard(FakeTensorImpl* fake,
+                              const std::vector<int64_t>& shard_sizes,
+                              const ShardWindow& w) {
+  const at::Tensor& meta = fake->meta_tensor();
+  std::lock_guard<std::recursive_mutex> lock{tape_mutex};
+  auto rec = getRecord(fake);
+  auto nodes = buildCallStack(*rec);
+  std::vector<ChainStep> steps;
+  steps.reserve(nodes.size());
+  for (const auto& n : nodes) {
+    steps.push_back(classifyChainNode(*n));
+  }
+  TORCH_CHECK(!steps.empty() &&
+                  (steps.front().kind == ChainStep::Kind::kFactory ||
+                   steps.front().kind == ChainStep::Kind::kZero ||
+                   steps.front().kind == ChainStep::Kind::kFill),
+              "slice materialization: the tape does not start with a "
+              "factory op");
+
+  at::Tensor shard = at::empty(
+      shard_sizes, at::TensorOptions()
+                       .dtype(meta.scalar_type())
+                       .device(fake->fake_device()));
+  // A trailing [RNG step, fusable tail...] run is one fused launch; any
+  // other arrangement applies step by step.
+  const std::optional<size_t> fused_at =
+      fusedRunStart(steps, meta.scalar_type(), meta.numel());
+  for (size_t i = 0; i < steps.size(); ++i) {
+    if (fused_at.has_value() && i == *fused_at) {
+      std::vector<TailOp> tail;
+      for (++i; i < steps.size() &&
+                steps[i].kind == ChainStep::Kind::kPointwise;
+           ++i) {
+        tail.push_back(*steps[i].tail_op);
+      }
+      applyFusedShardStep(steps[*fused_at], tail, shard, w, meta.numel());
+      break;  // only pass steps remain
+    }
+    applyShardStep(steps[i], shard, w, meta.numel());
+  }
+  return shard;
+}
+
 }  // namespace
 
 const char* tailOpName(int32_t op) {
@@ -1733,47 +1819,54 @@ at::Tensor materializeTensorShard(const at::Tensor& tensor,
   const ShardWindow w{n_blocks, (end_row - start_row) * inner,
                       dim_len * inner, start_row * inner};
 
-  std::lock_guard<std::recursive_mutex> lock{tape_mutex};
-  auto rec = getRecord(fake);
-  auto nodes = buildCallStack(*rec);
-  std::vector<ChainStep> steps;
-  steps.reserve(nodes.size());
-  for (const auto& n : nodes) {
-    steps.push_back(classifyChainNode(*n));
-  }
-  TORCH_CHECK(!steps.empty() &&
-                  (steps.front().kind == ChainStep::Kind::kFactory ||
-                   steps.front().kind == ChainStep::Kind::kZero ||
-                   steps.front().kind == ChainStep::Kind::kFill),
-              "slice materialization: the tape does not start with a "
-              "factory op");
-
   std::vector<int64_t> shard_sizes(meta.sizes().begin(), meta.sizes().end());
   if (!shard_sizes.empty()) {
     shard_sizes[dim] = end_row - start_row;
   }
-  at::Tensor shard = at::empty(
-      shard_sizes, at::TensorOptions()
-                       .dtype(meta.scalar_type())
-                       .device(fake->fake_device()));
-  // A trailing [RNG step, fusable tail...] run is one fused launch; any
-  // other arrangement applies step by step.
-  const std::optional<size_t> fused_at =
-      fusedRunStart(steps, meta.scalar_type(), meta.numel());
-  for (size_t i = 0; i < steps.size(); ++i) {
-    if (fused_at.has_value() && i == *fused_at) {
-      std::vector<TailOp> tail;
-      for (++i; i < steps.size() &&
-                steps[i].kind == ChainStep::Kind::kPointwise;
-           ++i) {
-        tail.push_back(*steps[i].tail_op);
-      }
-      applyFusedShardStep(steps[*fused_at], tail, shard, w, meta.numel());
-      break;  // only pass steps remain
-    }
-    applyShardStep(steps[i], shard, w);
+  return replayChainOnShard(fake, shard_sizes, w);
+}
+
+at::Tensor materializeTensorBlock(const at::Tensor& tensor,
+                                  at::IntArrayRef starts,
+                                  at::IntArrayRef ends) {
+  auto* fake = asFake(tensor);
+  TORCH_CHECK_VALUE(fake != nullptr && getRecord(fake) != nullptr,
+                    "`tensor` is not a deferred tensor.");
+  const at::Tensor& meta = fake->meta_tensor();
+  TORCH_CHECK(meta.is_contiguous(),
+              "slice materialization requires a contiguous tensor");
+  const int64_t rank = meta.dim();
+  TORCH_CHECK(static_cast<int64_t>(starts.size()) == rank &&
+                  static_cast<int64_t>(ends.size()) == rank,
+              "block materialization takes one start and one end per dim: "
+              "got ", starts.size(), " and ", ends.size(), " for a ", rank,
+              "-d tensor");
+  std::vector<int64_t> shard_sizes(rank);
+  for (int64_t d = 0; d < rank; ++d) {
+    TORCH_CHECK(0 <= starts[d] && starts[d] <= ends[d] &&
+                    ends[d] <= meta.size(d),
+                "invalid slice range [", starts[d], ", ", ends[d],
+                ") for size ", meta.size(d), " along dim ", d);
+    shard_sizes[d] = ends[d] - starts[d];
   }
-  return shard;
+  BoxGeometry box;
+  const BoxStatus status = normalizeBox(meta.sizes().data(), starts.data(),
+                                        ends.data(), static_cast<int>(rank),
+                                        &box);
+  TORCH_CHECK(status == BoxStatus::kOk,
+              "slice materialization: the block needs more than ",
+              kMaxBoxLevels, " nested strided levels; materialize the "
+              "tensor fully instead.");
+  // 0 and 1 levels are the flat range and the single-dim window, served
+  // by the ops materializeTensorShard launches; deeper nests take the box
+  // op.
+  ShardWindow w{1, box.run_len, box.run_len, box.g_off};
+  if (box.levels == 1) {
+    w = ShardWindow{box.extent[0], box.run_len, box.g_stride[0], box.g_off};
+  } else if (box.levels >= 2) {
+    w.box = box;
+  }
+  return replayChainOnShard(fake, shard_sizes, w);
 }
 
 at::Tensor materializeTensor(const at::Tensor& tensor) {

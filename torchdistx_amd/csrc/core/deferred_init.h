@@ -134,4 +134,19 @@ at::Tensor materializeTensorShard(const at::Tensor& tensor,
                                   int64_t end_row,
                                   int64_t dim = 0);
 
+// N-d form of materializeTensorShard: materializes the block
+// full[starts[0]:ends[0], ..., starts[r-1]:ends[r-1]] alone (one entry per
+// tensor dim; a 0-d tensor takes empty lists), bitwise-equal to that
+// block of a full materialization. This is the 2-D mesh primitive (FSDP x
+// TP, or EP x TP on stacked expert weights): a rank generates exactly the
+// elements it keeps. The block is normalized into nested contiguous runs
+// (csrc/core/box_geometry.h); flat ranges and single-dim windows launch
+// the ops materializeTensorShard launches, deeper nests tdx::rng_box_.
+// Same supported tapes and errors as materializeTensorShard; a block that
+// needs more than kMaxBoxLevels (4) nested levels throws the same
+// "slice materialization" error.
+at::Tensor materializeTensorBlock(const at::Tensor& tensor,
+                                  at::IntArrayRef starts,
+                                  at::IntArrayRef ends);
+
 }  // namespace tdx

@@ -188,4 +188,21 @@ PYBIND11_MODULE(_C, m) {
         "Materializes indices [start_row, end_row) of the deferred tensor "
         "along `dim` alone, bitwise-equal to that slice of a full native "
         "materialization (see docs/distributed_materialization.md).");
+
+  m.def("materialize_tensor_block",
+        [](const at::Tensor& t, std::vector<int64_t> starts,
+           std::vector<int64_t> ends) {
+          at::Tensor out;
+          {
+            pybind11::gil_scoped_release release;
+            out = tdx::materializeTensorBlock(t, starts, ends);
+          }
+          return out;
+        },
+        pybind11::arg("tensor"), pybind11::arg("starts"),
+        pybind11::arg("ends"),
+        "Materializes the block tensor[starts[0]:ends[0], ..., "
+        "starts[r-1]:ends[r-1]] of the deferred tensor alone (one entry per "
+        "dim), bitwise-equal to that block of a full native "
+        "materialization (see docs/distributed_materialization.md).");
 }

@@ -19,6 +19,7 @@
 #include <ATen/ScalarOps.h>
 #include <torch/library.h>
 
+#include "box_geometry.h"
 #include "deferred_init.h"
 #include "philox.h"
 
@@ -396,6 +397,97 @@ at::Tensor& cpu_rng_chain_shard_win_(
   return shard;
 }
 
+// N-d box (csrc/core/box_geometry.h): the shard is prod(extents) runs of
+// run_len contiguous global elements each, so the CPU form is the flat
+// range fill once per run, then the tail ops on the shard. CUDA twin:
+// csrc/hip/init_kernels.hip rng_box_kernel.
+template <RngKind kKind>
+void cpuPhiloxBox(at::Tensor& shard, const BoxGeometry& geo, float a,
+                  float b, uint64_t seed, uint64_t offset) {
+  auto run = [&](auto* out) {
+    using T = std::remove_pointer_t<decltype(out)>;
+    const int64_t rows = geo.rows();
+    for (int64_t r = 0; r < rows; ++r) {
+      const int64_t lo = geo.rowStart(r);
+      cpuPhiloxRange<T, kKind>(out + r * geo.run_len, lo, lo + geo.run_len,
+                               a, b, seed, offset);
+    }
+  };
+  switch (shard.scalar_type()) {
+    case at::kFloat:
+      run(shard.data_ptr<float>());
+      break;
+    case at::kBFloat16:
+      run(shard.data_ptr<at::BFloat16>());
+      break;
+    default:
+      run(shard.data_ptr<at::Half>());
+      break;
+  }
+}
+
+at::Tensor& cpu_rng_box_(at::Tensor& shard, at::IntArrayRef extents,
+                         at::IntArrayRef g_strides, int64_t run_len,
+                         int64_t g_off, int64_t dist, double p0, double p1,
+                         at::IntArrayRef tail_ops,
+                         at::ArrayRef<double> tail_s0,
+                         at::ArrayRef<double> tail_s1, int64_t full_numel,
+                         int64_t seed, int64_t offset) {
+  TORCH_CHECK(shard.is_contiguous(),
+              "tdx CPU init requires contiguous tensors");
+  const char* err =
+      checkBoxArgs(extents.data(), extents.size(), g_strides.data(),
+                   g_strides.size(), run_len, g_off, shard.numel(),
+                   full_numel);
+  TORCH_CHECK(err == nullptr, "rng_box: ", err);
+  cpuCheckTail(tail_ops, tail_s0, tail_s1);
+  for (int64_t op : tail_ops) {
+    TORCH_CHECK(TailOp::kErfinv <= op && op <= TailOp::kAbs,
+                "rng_chain: bad tail opcode ", op);
+  }
+  TORCH_CHECK(dist != 1 || p1 >= 0.0,
+              "normal_ expects std >= 0.0, but found std=", p1);
+  TORCH_CHECK(dist != 2 || (0.0 <= p0 && p0 <= 1.0),
+              "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
+  TORCH_CHECK(0 <= dist && dist <= 2,
+              "rng_box: dist must be 0 (uniform), 1 (normal) or 2 "
+              "(bernoulli), got ", dist);
+  TORCH_CHECK(shard.scalar_type() == at::kFloat ||
+                  shard.scalar_type() == at::kBFloat16 ||
+                  shard.scalar_type() == at::kHalf,
+              "tdx box kernel supports float32/bf16/fp16, got ",
+              shard.scalar_type());
+  if (shard.numel() == 0) {
+    return shard;
+  }
+  BoxGeometry geo;
+  geo.g_off = g_off;
+  geo.run_len = run_len;
+  geo.levels = static_cast<int32_t>(extents.size());
+  for (int l = 0; l < geo.levels; ++l) {
+    geo.extent[l] = extents[l];
+    geo.g_stride[l] = g_strides[l];
+  }
+  const auto s = static_cast<uint64_t>(seed);
+  const auto o = static_cast<uint64_t>(offset);
+  switch (dist) {
+    case 0:
+      cpuPhiloxBox<RngKind::kUniform>(shard, geo, static_cast<float>(p0),
+                                      static_cast<float>(p1 - p0), s, o);
+      break;
+    case 1:
+      cpuPhiloxBox<RngKind::kNormal>(shard, geo, static_cast<float>(p0),
+                                     static_cast<float>(p1), s, o);
+      break;
+    default:
+      cpuPhiloxBox<RngKind::kBernoulli>(shard, geo, static_cast<float>(p0),
+                                        0.0f, s, o);
+      break;
+  }
+  cpuApplyTail(shard, tail_ops, tail_s0, tail_s1);
+  return shard;
+}
+
 at::Tensor& cpu_rng_chain_(at::Tensor& self, int64_t dist, double p0,
                            double p1, at::IntArrayRef tail_ops,
                            at::ArrayRef<double> tail_s0,
@@ -458,6 +550,14 @@ TORCH_LIBRARY(tdx, m) {
       "int g_stride, int g_off, int dist, float p0, float p1, "
       "int[] tail_ops, float[] tail_s0, float[] tail_s1, int full_numel, "
       "*, int seed, int offset) -> Tensor(a!)");
+  // An N-d box of the full tensor in normalized form (box_geometry.h):
+  // extents/g_strides per level, outermost first. Empty tail lists mean
+  // no tail.
+  m.def(
+      "rng_box_(Tensor(a!) shard, int[] extents, int[] g_strides, "
+      "int run_len, int g_off, int dist, float p0, float p1, "
+      "int[] tail_ops, float[] tail_s0, float[] tail_s1, int full_numel, "
+      "int seed, int offset) -> Tensor(a!)");
 }
 
 TORCH_LIBRARY_IMPL(tdx, CPU, m) {
@@ -475,6 +575,7 @@ TORCH_LIBRARY_IMPL(tdx, CPU, m) {
   m.impl("bernoulli_shard_win_", cpu_bernoulli_shard_win_);
   m.impl("rng_chain_", cpu_rng_chain_);
   m.impl("rng_chain_shard_win_", cpu_rng_chain_shard_win_);
+  m.impl("rng_box_", cpu_rng_box_);
 }
 
 }  // namespace

@@ -28,10 +28,14 @@
 #include <ATen/hip/HIPGeneratorImpl.h>
 #include <torch/library.h>
 
+#include <cstdlib>
 #include <limits>
+#include <type_traits>
 
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
+
+#include "../core/box_geometry.h"
 
 namespace tdx {
 namespace {
@@ -1095,6 +1099,271 @@ at::Tensor& tdx_rng_chain_(at::Tensor& self, int64_t dist, double p0,
                                   self.numel(), seed, offset);
 }
 
+// ---------------------------------------------------------------------------
+// N-d box kernel: materializes full[lo_0:hi_0, ..., lo_{r-1}:hi_{r-1}] of a
+// contiguous virtual full tensor. The box arrives normalized (BoxGeometry
+// in csrc/core/box_geometry.h): equally long contiguous runs nested under
+// up to kMaxBoxLevels strided levels — rng_chain_window_kernel's geometry
+// with more than one level. A shard unit (a 16-byte group on the vector
+// path, an element otherwise) splits into its run and its place within
+// the run; the run index is decomposed innermost level first, and every
+// coordinate adds its level's stride to the GLOBAL unit index. From there
+// on the value is computed exactly as in the kernels above (same group
+// id, lane, from_float barrier and tail), so a box is bitwise a sub-tensor
+// of the full materialization.
+// The decomposition costs one division per level. On the 32-bit index
+// path those are multiply-shift divisions by host-computed magics
+// (MagicDiv32); the 64-bit path (shards of 2^31 elements or more) divides
+// plainly.
+// ---------------------------------------------------------------------------
+
+// Geometry in UNITS (groups on the vector path, elements otherwise).
+// Levels are outermost first; only levels 1.. are divided by (the
+// outermost coordinate is what remains of the run index).
+template <typename IdxT>
+struct BoxArgs {
+  uint64_t g0;
+  uint64_t gs[kMaxBoxLevels];
+  IdxT run;
+  IdxT ext[kMaxBoxLevels];
+  int32_t levels;
+  // Magics and shifts (MagicDiv32) of `run` and of ext[1..]; unused on
+  // the plain-division paths.
+  uint32_t run_magic, run_shift;
+  uint32_t ext_magic[kMaxBoxLevels - 1];
+  uint32_t ext_shift[kMaxBoxLevels - 1];
+};
+
+template <typename IdxT, bool kMagic>
+__device__ __forceinline__ IdxT boxDiv(IdxT n, IdxT d, uint32_t magic,
+                                       uint32_t shift) {
+  if constexpr (kMagic) {
+    static_assert(std::is_same_v<IdxT, uint32_t>,
+                  "the multiply-shift divisor is exact below 2^31 only");
+    return magicDiv(MagicDiv32{d, magic, shift}, n);
+  } else {
+    return n / d;
+  }
+}
+
+// Global unit index of shard unit j.
+template <typename IdxT, bool kMagic>
+__device__ __forceinline__ uint64_t boxGlobalUnit(const BoxArgs<IdxT>& box,
+                                                  IdxT j) {
+  IdxT row = boxDiv<IdxT, kMagic>(j, box.run, box.run_magic, box.run_shift);
+  const IdxT within = j - row * box.run;
+  uint64_t u = box.g0 + within;
+#pragma unroll
+  for (int l = kMaxBoxLevels - 1; l >= 1; --l) {
+    if (l < box.levels) {
+      const IdxT q = boxDiv<IdxT, kMagic>(
+          row, box.ext[l], box.ext_magic[l - 1], box.ext_shift[l - 1]);
+      u += static_cast<uint64_t>(row - q * box.ext[l]) * box.gs[l];
+      row = q;
+    }
+  }
+  return u + static_cast<uint64_t>(row) * box.gs[0];
+}
+
+// `vec`: the host's check that `out` is 16-byte aligned and that g_off,
+// run_len and every stride are group multiples — `box` is then in groups
+// and every group of the box is whole. `n_units` is the shard's group
+// (vec) or element count. kHasTail == false carries no tail code.
+template <typename T, Dist kDist, typename IdxT, bool kHasTail, bool kMagic>
+__global__ void rng_box_kernel(T* __restrict__ out,
+                               BoxArgs<IdxT> box,
+                               IdxT n_units,
+                               bool vec,
+                               float a,
+                               float b,
+                               uint64_t seed,
+                               uint64_t offset,
+                               TailProgram prog) {
+  constexpr int kElems = VecTraits<T>::kElems;
+  using Vec = typename VecTraits<T>::Vec;
+  const IdxT stride = static_cast<IdxT>(gridDim.x) * blockDim.x;
+  if (vec) {
+    for (IdxT j = blockIdx.x * static_cast<IdxT>(blockDim.x) + threadIdx.x;
+         j < n_units; j += stride) {
+      const uint64_t g = boxGlobalUnit<IdxT, kMagic>(box, j);
+      float vals[kElems];
+      rngGroupValues<T, kDist>(g, a, b, seed, offset, vals);
+      if constexpr (kHasTail) {
+        applyTail<T, kElems>(vals, prog, g * kElems);
+      }
+      Vec v;
+      T* vp = reinterpret_cast<T*>(&v);
+#pragma unroll
+      for (int e = 0; e < kElems; ++e) {
+        vp[e] = from_float<T>(vals[e]);
+      }
+      *reinterpret_cast<Vec*>(out + static_cast<uint64_t>(j) * kElems) = v;
+    }
+    return;
+  }
+  for (IdxT i = blockIdx.x * static_cast<IdxT>(blockDim.x) + threadIdx.x;
+       i < n_units; i += stride) {
+    const uint64_t ge = boxGlobalUnit<IdxT, kMagic>(box, i);
+    const uint64_t g = ge / kElems;
+    float vals[kElems];
+    rngGroupValues<T, kDist>(g, a, b, seed, offset, vals);
+    if constexpr (kHasTail) {
+      applyTail<T, kElems>(vals, prog, g * kElems);
+    }
+    out[i] = from_float<T>(vals[ge - g * kElems]);
+  }
+}
+
+// Benchmark switch (scripts/box_kernel_bench.py): with TDX_BOX_PLAIN_DIV=1
+// in the environment the untailed 32-bit normal kernels divide with `/`,
+// so one process can time both forms alternately.
+bool boxPlainDivRequested() {
+  const char* v = std::getenv("TDX_BOX_PLAIN_DIV");
+  return v != nullptr && v[0] == '1';
+}
+
+template <Dist kDist>
+void launchRngBox(at::Tensor& shard, const BoxGeometry& geo, double p0,
+                  double p1, const TailProgram& prog, int64_t seed,
+                  int64_t offset) {
+  float a = static_cast<float>(p0);
+  float b = kDist == Dist::kUniform ? static_cast<float>(p1 - p0)
+                                    : static_cast<float>(p1);
+  const int64_t numel = shard.numel();
+  const bool ptr_ok = reinterpret_cast<uintptr_t>(shard.data_ptr()) % 16 == 0;
+  const bool has_tail = prog.n > 0;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  auto launch = [&](auto type_tag) {
+    using T = decltype(type_tag);
+    constexpr int64_t kElems = VecTraits<T>::kElems;
+    bool vec = ptr_ok && geo.g_off % kElems == 0 && geo.run_len % kElems == 0;
+    for (int l = 0; l < geo.levels; ++l) {
+      vec = vec && geo.g_stride[l] % kElems == 0;
+    }
+    const int64_t unit = vec ? kElems : 1;
+    const int64_t n_units = numel / unit;  // vec: numel is a group multiple
+    const int64_t n_work = (numel + kElems - 1) / kElems;
+    auto launch_idx = [&](auto idx_tag, auto tail_tag, auto magic_tag) {
+      using IdxT = decltype(idx_tag);
+      constexpr bool kHasTail = decltype(tail_tag)::value;
+      constexpr bool kMagic = decltype(magic_tag)::value;
+      BoxArgs<IdxT> box{};
+      box.g0 = static_cast<uint64_t>(geo.g_off / unit);
+      box.run = static_cast<IdxT>(geo.run_len / unit);
+      box.levels = geo.levels;
+      for (int l = 0; l < kMaxBoxLevels; ++l) {
+        box.gs[l] = 0;
+        box.ext[l] = 1;
+      }
+      for (int l = 0; l < geo.levels; ++l) {
+        box.gs[l] = static_cast<uint64_t>(geo.g_stride[l] / unit);
+        box.ext[l] = static_cast<IdxT>(geo.extent[l]);
+      }
+      if constexpr (kMagic) {
+        const MagicDiv32 rd = makeMagicDiv32(static_cast<uint32_t>(box.run));
+        box.run_magic = rd.magic;
+        box.run_shift = rd.shift;
+        for (int l = 1; l < kMaxBoxLevels; ++l) {
+          const MagicDiv32 ed =
+              makeMagicDiv32(static_cast<uint32_t>(box.ext[l]));
+          box.ext_magic[l - 1] = ed.magic;
+          box.ext_shift[l - 1] = ed.shift;
+        }
+      }
+      hipLaunchKernelGGL(
+          (rng_box_kernel<T, kDist, IdxT, kHasTail, kMagic>),
+          dim3(numBlocks(n_work)), dim3(kBlock), 0, stream.stream(),
+          reinterpret_cast<T*>(shard.data_ptr()), box,
+          static_cast<IdxT>(n_units), vec, a, b,
+          static_cast<uint64_t>(seed), static_cast<uint64_t>(offset), prog);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
+    };
+    if (numel > std::numeric_limits<int32_t>::max()) {
+      if (has_tail) {
+        launch_idx(int64_t{}, std::true_type{}, std::false_type{});
+      } else {
+        launch_idx(int64_t{}, std::false_type{}, std::false_type{});
+      }
+    } else if (has_tail) {
+      launch_idx(uint32_t{}, std::true_type{}, std::true_type{});
+    } else if (kDist == Dist::kNormal && boxPlainDivRequested()) {
+      if constexpr (kDist == Dist::kNormal) {
+        launch_idx(uint32_t{}, std::false_type{}, std::false_type{});
+      }
+    } else {
+      launch_idx(uint32_t{}, std::false_type{}, std::true_type{});
+    }
+  };
+  switch (shard.scalar_type()) {
+    case at::kFloat:
+      launch(float{});
+      break;
+    case at::kBFloat16:
+      launch(__hip_bfloat16{});
+      break;
+    case at::kHalf:
+      launch(__half{});
+      break;
+    default:
+      TORCH_CHECK(false, "tdx box kernel supports float32/bf16/fp16, got ",
+                  shard.scalar_type());
+  }
+}
+
+at::Tensor& tdx_rng_box_(at::Tensor& shard, at::IntArrayRef extents,
+                         at::IntArrayRef g_strides, int64_t run_len,
+                         int64_t g_off, int64_t dist, double p0, double p1,
+                         at::IntArrayRef tail_ops,
+                         at::ArrayRef<double> tail_s0,
+                         at::ArrayRef<double> tail_s1, int64_t full_numel,
+                         int64_t seed, int64_t offset) {
+  TORCH_CHECK(shard.is_contiguous(),
+              "tdx shard kernels require contiguous tensors");
+  const char* err =
+      checkBoxArgs(extents.data(), extents.size(), g_strides.data(),
+                   g_strides.size(), run_len, g_off, shard.numel(),
+                   full_numel);
+  TORCH_CHECK(err == nullptr, "rng_box: ", err);
+  const TailProgram prog =
+      makeTailProgram(tail_ops, tail_s0, tail_s1, full_numel);
+  TORCH_CHECK(dist != 1 || p1 >= 0.0,
+              "normal_ expects std >= 0.0, but found std=", p1);
+  TORCH_CHECK(dist != 2 || (0.0 <= p0 && p0 <= 1.0),
+              "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
+  TORCH_CHECK(0 <= dist && dist <= 2,
+              "rng_box: dist must be 0 (uniform), 1 (normal) or 2 "
+              "(bernoulli), got ", dist);
+  TORCH_CHECK(shard.scalar_type() == at::kFloat ||
+                  shard.scalar_type() == at::kBFloat16 ||
+                  shard.scalar_type() == at::kHalf,
+              "tdx box kernel supports float32/bf16/fp16, got ",
+              shard.scalar_type());
+  if (shard.numel() == 0) {
+    return shard;
+  }
+  BoxGeometry geo;
+  geo.g_off = g_off;
+  geo.run_len = run_len;
+  geo.levels = static_cast<int32_t>(extents.size());
+  for (int l = 0; l < geo.levels; ++l) {
+    geo.extent[l] = extents[l];
+    geo.g_stride[l] = g_strides[l];
+  }
+  switch (dist) {
+    case 0:
+      launchRngBox<Dist::kUniform>(shard, geo, p0, p1, prog, seed, offset);
+      break;
+    case 1:
+      launchRngBox<Dist::kNormal>(shard, geo, p0, p1, prog, seed, offset);
+      break;
+    default:
+      launchRngBox<Dist::kBernoulli>(shard, geo, p0, 0.0, prog, seed,
+                                     offset);
+      break;
+  }
+  return shard;
+}
+
 at::Tensor& tdx_fill_(at::Tensor& self, const at::Scalar& value) {
   TORCH_CHECK(self.is_contiguous(),
               "tdx init kernels require contiguous tensors");
@@ -1545,6 +1814,7 @@ TORCH_LIBRARY_IMPL(tdx, CUDA, m) {
   m.impl("bernoulli_shard_win_", tdx_bernoulli_shard_win_);
   m.impl("rng_chain_", tdx_rng_chain_);
   m.impl("rng_chain_shard_win_", tdx_rng_chain_shard_win_);
+  m.impl("rng_box_", tdx_rng_box_);
 }
 
 }  // namespace

@@ -54,6 +54,7 @@ PYBIND11_MODULE(_K, m) {
   m.def("has_anyprecision_adamw_batched", [] { return true; });
   m.def("has_batched_init", [] { return true; });
   m.def("has_fused_chains", [] { return true; });
+  m.def("has_box_kernel", [] { return true; });
 
   m.def("batched_init_", &tdx::batched_init_launch,
         pybind11::arg("tensors"), pybind11::arg("dists"),

@@ -28,7 +28,7 @@
 #     trusted to share RNG state (e.g. mixed seeds) but must end
 #     bitwise-identical.
 
-from typing import Callable, Dict, List, Optional, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import torch
 import torch.distributed as dist
@@ -430,6 +430,48 @@ def materialize_tensor_shard(
     return shard
 
 
+def materialize_tensor_block(
+    tensor: torch.Tensor,
+    ranges: Sequence[Optional[Tuple[int, int]]],
+) -> torch.Tensor:
+    """Materializes the block ``tensor[s0:e0, s1:e1, ...]`` of a deferred
+    tensor without touching the rest — bitwise-equal to that block of a
+    full native materialization, and generating only the elements kept.
+    ``ranges`` has one entry per dim: ``(start, end)``, or ``None`` for
+    the whole dim. This is the N-d form of `materialize_tensor_shard` and
+    the primitive for 2-D layouts (FSDP x TP, or EP x TP on stacked
+    ``[E, out, in]`` expert weights). Unsupported tapes, and blocks that
+    need more than four nested strided levels, fall back to
+    `materialize_tensor` + slicing."""
+    if len(ranges) != tensor.dim():
+        raise ValueError(
+            f"materialize_tensor_block expects one range per dim: got "
+            f"{len(ranges)} for a {tensor.dim()}-d tensor"
+        )
+    starts, ends = [], []
+    for d, r in enumerate(ranges):
+        start, end = (0, tensor.shape[d]) if r is None else r
+        starts.append(int(start))
+        ends.append(int(end))
+    try:
+        block = _C.materialize_tensor_block(tensor, starts, ends)
+    except RuntimeError as e:
+        if "slice materialization" not in str(e):
+            raise
+        # Same fallback as materialize_tensor_shard: the full tensor
+        # once, then the block of it.
+        full = _C.materialize_tensor(tensor)
+        if full.dim() > 0:
+            block = full[
+                tuple(slice(s, e) for s, e in zip(starts, ends))
+            ].clone()
+        else:
+            block = full
+    if tensor.requires_grad:
+        block.requires_grad_(True)
+    return block
+
+
 def materialize_module_dim0_sharded(
     module: Module,
     rank: Optional[int] = None,
@@ -515,28 +557,72 @@ def materialize_module_tp_sharded(
     return out
 
 
+def _local_box(shape, device_mesh, placements, name: str):
+    """This rank's block of a tensor of ``shape`` under ``placements`` (one
+    per mesh dim), as [(start, end)] per tensor dim: the placements apply
+    left to right, each ``Shard(d)`` splitting the CURRENT local range of
+    dim d with torch.chunk semantics (ceil-size slots, short or empty
+    tail) — so two mesh dims sharding one tensor dim nest, as in
+    ``distribute_tensor``."""
+    from torch.distributed.tensor import Replicate, Shard
+
+    ranges = [(0, n) for n in shape]
+    for mesh_dim, p in enumerate(placements):
+        if isinstance(p, Replicate):
+            continue
+        # Exact type: _StridedShard subclasses Shard but interleaves.
+        if type(p) is not Shard:
+            raise ValueError(
+                f"materialize_module_dtensor: unsupported placement {p!r} "
+                f"for {name!r} (only Shard(dim) and Replicate() are)"
+            )
+        if not -len(shape) <= p.dim < len(shape):
+            raise ValueError(
+                f"materialize_module_dtensor: {p!r} is out of range for "
+                f"{name!r}, a {len(shape)}-d tensor"
+            )
+        d = p.dim % len(shape)
+        lo, hi = ranges[d]
+        n = hi - lo
+        world = device_mesh.size(mesh_dim)
+        rank = device_mesh.get_local_rank(mesh_dim)
+        slot = -(-n // world)
+        start = min(rank * slot, n)
+        ranges[d] = (lo + start, lo + min(start + slot, n))
+    return ranges
+
+
 def materialize_module_dtensor(
     module: Module,
     device_mesh,
-    shard_dims: Optional[Dict[str, int]] = None,
+    shard_dims: Optional[Dict[str, object]] = None,
 ) -> Dict[str, "torch.Tensor"]:
     """FSDP2-era init: every parameter/buffer of the deferred ``module``
-    materializes directly as a ``DTensor`` over the given 1-D device
-    mesh — each rank slice-materializes only its local chunk
-    (torch.chunk split semantics, matching ``distribute_tensor``), so
-    the full model never exists on any device. By default every tensor
-    shards on dim 0 (the FSDP2 ``fully_shard`` layout); ``shard_dims``
-    overrides the split dim per fully-qualified name (e.g. dim 1 for
-    row-parallel TP weights), with ``None`` meaning ``Replicate()`` —
-    the rank then fully materializes that tensor (bitwise-identical
-    everywhere, zero communication). Returns {fqn -> DTensor}."""
+    materializes directly as a ``DTensor`` over the given device mesh —
+    each rank materializes only its local chunk (torch.chunk split
+    semantics, matching ``distribute_tensor``), so the full model never
+    exists on any device.
+
+    On a 1-D mesh every tensor shards on dim 0 by default (the FSDP2
+    ``fully_shard`` layout); ``shard_dims`` overrides the split dim per
+    fully-qualified name (e.g. dim 1 for row-parallel TP weights), with
+    ``None`` meaning ``Replicate()`` — the rank then fully materializes
+    that tensor (bitwise-identical everywhere, zero communication).
+
+    On an N-d mesh (FSDP x TP, EP x TP) the default is ``Shard(0)`` on
+    mesh dim 0 and ``Replicate()`` on the others, the data-parallel by
+    tensor-parallel convention; an int or ``None`` in ``shard_dims`` sets
+    mesh dim 0 likewise. On any mesh a ``shard_dims`` value may also be a
+    sequence of ``Shard(d)`` / ``Replicate()`` placements, one per mesh
+    dim: the rank then materializes exactly its N-d block
+    (`materialize_tensor_block`). Other placement types raise
+    ``ValueError``. Returns {fqn -> DTensor}."""
     from torch.distributed.tensor import DTensor, Replicate, Shard
 
-    if device_mesh.ndim != 1:
-        raise ValueError("materialize_module_dtensor expects a 1-D mesh")
-    world = device_mesh.size()
-    rank = device_mesh.get_local_rank()
     shard_dims = shard_dims or {}
+    one_d = device_mesh.ndim == 1
+    world = device_mesh.size() if one_d else None
+    rank = device_mesh.get_local_rank() if one_d else None
 
     out: Dict[str, torch.Tensor] = {}
     for name, t in list(module.named_parameters()) + list(
@@ -545,6 +631,36 @@ def materialize_module_dtensor(
         if not _C.can_materialize(t):
             continue
         dim = shard_dims.get(name, 0)
+        if not (dim is None or isinstance(dim, int)) or not one_d:
+            # Placements per mesh dim: this rank's N-d block.
+            if dim is None or isinstance(dim, int):
+                # Mesh dim 0 takes the 1-D meaning, the rest replicate.
+                # (A 0-d tensor has no dim to shard by default.)
+                first = (
+                    Replicate() if dim is None or t.dim() == 0 else Shard(dim)
+                )
+                placements = [first] + [Replicate()] * (device_mesh.ndim - 1)
+            else:
+                placements = list(dim)
+                if len(placements) != device_mesh.ndim:
+                    raise ValueError(
+                        f"shard_dims[{name!r}] has {len(placements)} "
+                        f"placements for a {device_mesh.ndim}-d mesh"
+                    )
+            ranges = _local_box(t.shape, device_mesh, placements, name)
+            placements = [
+                Shard(p.dim % t.dim()) if isinstance(p, Shard) else p
+                for p in placements
+            ]
+            if all(isinstance(p, Replicate) for p in placements):
+                local = _C.materialize_tensor(t)
+            else:
+                local = materialize_tensor_block(t, ranges)
+            out[name] = DTensor.from_local(
+                local, device_mesh, placements, run_check=False,
+                shape=t.shape, stride=t.stride(),
+            )
+            continue
         if dim is None:
             full = _C.materialize_tensor(t)
             out[name] = DTensor.from_local(
