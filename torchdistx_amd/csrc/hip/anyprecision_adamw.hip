@@ -7,8 +7,9 @@
 // Kahan-compensated weight update — in ONE pass: 4-5 reads + 3-4 writes per
 // element instead of ~20, which is the entire win for a memory-bound op.
 //
-// All arithmetic is fp32; tensor elements are converted at load/store per
-// their runtime dtype (f32 / bf16 / f16 in any combination). The per-access
+// All arithmetic is fp32 (but lerpMomentum); tensor elements are
+// converted at load/store per their runtime dtype (f32 / bf16 / f16 in
+// any combination). The per-access
 // dtype switch is wave-uniform and fully predicted, so on this
 // memory-bound kernel it costs nothing measurable; a vectorized
 // specialization for the flagship (bf16 param / f32 momentum / bf16
@@ -62,6 +63,20 @@ __device__ __forceinline__ void storef(void* p, DT dt, int64_t i, float v) {
   }
 }
 
+// m + w * (g - m), rounded once. Where g is close to -m * (1 - w) / w
+// (g ~ -9 m at beta1 = 0.9) the result cancels, and the fp32 rounding
+// errors of g - m and of the product, a few 2^-24 (|m| + |g|), would be
+// thousands of ulps of it; the update is step_size * exp_avg / denom and
+// would inherit them, which next to a parameter much smaller than the
+// update is far outside the fp32 rounding of that parameter. Two fp32
+// operands differ and multiply exactly enough in fp64 (full rate on
+// CDNA), so the momentum alone is formed there: five VALU ops.
+__device__ __forceinline__ float lerpMomentum(float m, float g, float w) {
+  const double md = m;
+  return static_cast<float>(
+      fma(static_cast<double>(w), static_cast<double>(g) - md, md));
+}
+
 // Vector packs: 8 elements per thread per iteration, 16-byte accesses for
 // 16-bit types, 2x16-byte for fp32.
 template <typename T>
@@ -110,6 +125,12 @@ struct AdamWScalars {
   float weight_decay;
   float step_size;
   float bias_correction2_sqrt;
+  // Complements formed in double on the host and narrowed once, as ATen
+  // forms its lerp_/addcmul_/mul_ scalars: 1.0f - beta2 formed from the
+  // narrowed beta2 is 111 fp32 ulps from float(1 - 0.999).
+  float one_minus_beta1;
+  float one_minus_beta2;
+  float decay;  // 1 - lr * weight_decay
 };
 
 // Vectorized fused step: 8 elements per thread per grid-stride iteration,
@@ -140,10 +161,10 @@ __global__ void adamw_vec_kernel(Tp* __restrict__ param,
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       if (s.weight_decay != 0.0f) {
-        p[j] *= 1.0f - s.lr * s.weight_decay;
+        p[j] *= s.decay;
       }
-      m[j] += (1.0f - s.beta1) * (gr[j] - m[j]);
-      v[j] = v[j] * s.beta2 + gr[j] * gr[j] * (1.0f - s.beta2);
+      m[j] = lerpMomentum(m[j], gr[j], s.one_minus_beta1);
+      v[j] = v[j] * s.beta2 + gr[j] * gr[j] * s.one_minus_beta2;
       const float denom = sqrtf(v[j]) / s.bias_correction2_sqrt + s.eps;
       const float update = -s.step_size * (m[j] / denom);
       if constexpr (kKahan) {
@@ -204,6 +225,9 @@ struct AdamWArgs {
   float weight_decay;
   float step_size;
   float bias_correction2_sqrt;
+  float one_minus_beta1;  // host-computed, see AdamWScalars
+  float one_minus_beta2;
+  float decay;
 };
 
 __global__ void anyprecision_adamw_kernel(AdamWArgs args) {
@@ -219,10 +243,10 @@ __global__ void anyprecision_adamw_kernel(AdamWArgs args) {
     float v = loadf(args.exp_avg_sq, args.dt_v, i);
 
     if (args.weight_decay != 0.0f) {
-      p *= 1.0f - args.lr * args.weight_decay;
+      p *= args.decay;
     }
-    m += (1.0f - args.beta1) * (g - m);
-    v = v * args.beta2 + g * g * (1.0f - args.beta2);
+    m = lerpMomentum(m, g, args.one_minus_beta1);
+    v = v * args.beta2 + g * g * args.one_minus_beta2;
 
     const float denom =
         sqrtf(v) / args.bias_correction2_sqrt + args.eps;
@@ -278,7 +302,8 @@ int64_t tryLaunchVec(const AdamWArgs& args, int grid, int block,
   }
   AdamWScalars s{n_full,         args.lr,       args.beta1,
                  args.beta2,     args.eps,      args.weight_decay,
-                 args.step_size, args.bias_correction2_sqrt};
+                 args.step_size, args.bias_correction2_sqrt,
+                 args.one_minus_beta1, args.one_minus_beta2, args.decay};
   bool launched = false;
   dispatch2(args.dt_param, [&](auto tp) {
     using Tp = decltype(tp);
@@ -346,6 +371,7 @@ struct BatchHeader {
   int32_t n_tensors;
   int64_t total_vblocks;
   float lr, beta1, beta2, eps, weight_decay;
+  float one_minus_beta1, one_minus_beta2, decay;  // see AdamWScalars
 };
 
 // blob layout: int64 prefix[n_tensors] then BatchTensorMeta[n_tensors].
@@ -381,10 +407,10 @@ __global__ void adamw_batched_kernel(const uint8_t* __restrict__ blob,
       float v = loadf(mt.exp_avg_sq, static_cast<DT>(mt.dt_v), i);
 
       if (h.weight_decay != 0.0f) {
-        p *= 1.0f - h.lr * h.weight_decay;
+        p *= h.decay;
       }
-      m += (1.0f - h.beta1) * (g - m);
-      v = v * h.beta2 + g * g * (1.0f - h.beta2);
+      m = lerpMomentum(m, g, h.one_minus_beta1);
+      v = v * h.beta2 + g * g * h.one_minus_beta2;
       const float denom = sqrtf(v) / mt.bias_correction2_sqrt + h.eps;
       const float update = -mt.step_size * (m / denom);
 
@@ -438,13 +464,19 @@ void anyprecision_adamw_step(at::Tensor& param,
                              double bias_correction2_sqrt) {
   TORCH_CHECK(param.is_cuda() && grad.is_cuda(),
               "fused AnyPrecisionAdamW requires GPU tensors");
-  const at::Tensor* checked[] = {&param, &grad, &exp_avg, &exp_avg_sq};
+  const at::Tensor* checked[] = {
+      &param, &grad, &exp_avg, &exp_avg_sq,
+      compensation.has_value() ? &*compensation : nullptr};
   for (const at::Tensor* t : checked) {
+    if (t == nullptr) {
+      continue;
+    }
     // Wrapper subclasses (DTensor, ...) reach C++ as storage-less impls;
     // dereferencing their null device pointer would be a GPU memory
-    // fault, so refuse them here rather than in the kernel.
-    TORCH_CHECK(t->unsafeGetTensorImpl()->has_storage() &&
-                    t->const_data_ptr() != nullptr,
+    // fault, so refuse them here rather than in the kernel. (An empty
+    // tensor's null pointer is never dereferenced.)
+    TORCH_CHECK(t->is_cuda() && t->unsafeGetTensorImpl()->has_storage() &&
+                    (t->numel() == 0 || t->const_data_ptr() != nullptr),
                 "fused AnyPrecisionAdamW requires plain dense tensors "
                 "(got a storage-less tensor, e.g. a DTensor wrapper)");
     TORCH_CHECK(t->is_contiguous(),
@@ -473,6 +505,9 @@ void anyprecision_adamw_step(at::Tensor& param,
   args.weight_decay = static_cast<float>(weight_decay);
   args.step_size = static_cast<float>(step_size);
   args.bias_correction2_sqrt = static_cast<float>(bias_correction2_sqrt);
+  args.one_minus_beta1 = static_cast<float>(1.0 - beta1);
+  args.one_minus_beta2 = static_cast<float>(1.0 - beta2);
+  args.decay = static_cast<float>(1.0 - lr * weight_decay);
 
   const int block = 256;
   const int grid = static_cast<int>(
@@ -511,6 +546,33 @@ void anyprecision_adamw_batched_step(
                   bias_correction2_sqrts.size() == n_tensors,
               "batched AdamW: list length mismatch");
 
+  int64_t total_vblocks = 0;
+  for (size_t t = 0; t < n_tensors; ++t) {
+    const at::Tensor& p = params[t];
+    const at::Tensor* checked[] = {
+        &p, &grads[t], &exp_avgs[t], &exp_avg_sqs[t],
+        compensations[t].has_value() ? &*compensations[t] : nullptr};
+    for (const at::Tensor* x : checked) {
+      if (x == nullptr) {
+        continue;
+      }
+      // An empty tensor may carry a null device pointer; it is never
+      // dereferenced (it owns no virtual block).
+      TORCH_CHECK(x->is_cuda() && x->is_contiguous() &&
+                      x->unsafeGetTensorImpl()->has_storage() &&
+                      (x->numel() == 0 || x->const_data_ptr() != nullptr) &&
+                      x->numel() == p.numel(),
+                  "batched AdamW: tensors must be plain dense contiguous "
+                  "GPU tensors of equal numel");
+    }
+    total_vblocks += (p.numel() + kBatchEPB - 1) / kBatchEPB;
+  }
+  if (total_vblocks == 0) {
+    // Every tensor is empty: nothing to update, and a zero-block grid is
+    // an invalid launch configuration.
+    return;
+  }
+
   const size_t prefix_bytes = sizeof(int64_t) * n_tensors;
   const size_t blob_bytes =
       prefix_bytes + sizeof(BatchTensorMeta) * n_tensors;
@@ -521,19 +583,9 @@ void anyprecision_adamw_batched_step(
   auto* metas = reinterpret_cast<BatchTensorMeta*>(
       static_cast<uint8_t*>(host_blob.data_ptr()) + prefix_bytes);
 
-  int64_t total_vblocks = 0;
+  total_vblocks = 0;
   for (size_t t = 0; t < n_tensors; ++t) {
     const at::Tensor& p = params[t];
-    const at::Tensor* checked[] = {&p, &grads[t], &exp_avgs[t],
-                                   &exp_avg_sqs[t]};
-    for (const at::Tensor* x : checked) {
-      TORCH_CHECK(x->is_cuda() && x->is_contiguous() &&
-                      x->unsafeGetTensorImpl()->has_storage() &&
-                      x->const_data_ptr() != nullptr &&
-                      x->numel() == p.numel(),
-                  "batched AdamW: tensors must be plain dense contiguous "
-                  "GPU tensors of equal numel");
-    }
     BatchTensorMeta& mt = metas[t];
     mt.param = p.data_ptr();
     mt.grad = grads[t].data_ptr();
@@ -567,6 +619,9 @@ void anyprecision_adamw_batched_step(
   h.beta2 = static_cast<float>(beta2);
   h.eps = static_cast<float>(eps);
   h.weight_decay = static_cast<float>(weight_decay);
+  h.one_minus_beta1 = static_cast<float>(1.0 - beta1);
+  h.one_minus_beta2 = static_cast<float>(1.0 - beta2);
+  h.decay = static_cast<float>(1.0 - lr * weight_decay);
 
   const int grid =
       static_cast<int>(std::min<int64_t>(total_vblocks, 16384));
