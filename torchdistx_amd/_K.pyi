@@ -10,6 +10,7 @@ def has_anyprecision_adamw_batched() -> bool: ...
 def has_batched_init() -> bool: ...
 def has_fused_chains() -> bool: ...
 def has_box_kernel() -> bool: ...
+def has_cast_chains() -> bool: ...
 def anyprecision_adamw_(
     param: torch.Tensor,
     grad: torch.Tensor,
@@ -48,4 +49,5 @@ def batched_init_(
     tail_ops: List[List[int]] = ...,
     tail_s0: List[List[float]] = ...,
     tail_s1: List[List[float]] = ...,
+    src_dtypes: Optional[List[Optional[torch.dtype]]] = None,
 ) -> None: ...

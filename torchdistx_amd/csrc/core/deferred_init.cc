@@ -91,6 +91,9 @@ struct RecordedOp {
   // Pinned Philox (seed, counter offset) for RNG ops; also consumed by the
   // slice-materialization fast path (materializeTensorShard).
   std::optional<std::pair<uint64_t, uint64_t>> philox;
+  // The dispatcher op, for ops recorded by the boxed fallback (not the
+  // tdx:: pseudo-ops): the chain model reads argument names off its schema.
+  std::optional<c10::OperatorHandle> handle;
 };
 
 // Pinned Philox state for recorded RNG ops: derived from the default
@@ -290,6 +293,23 @@ struct OpNode {
   std::optional<RecordedOp> op;          // dropped after replay
   std::vector<InputSlot> input_slots;    // tensor visit order over args
   std::vector<c10::Storage> output_storages;  // meta storages, visit order
+  // What each output looked like at record time (dtype Undefined for a
+  // non-fake output). Survives replay; the chain model needs the dtype a
+  // step runs at, which a later set_data or cast hides from the final
+  // tensor's metadata.
+  struct OutputMeta {
+    c10::ScalarType dtype = c10::ScalarType::Undefined;
+    c10::Device device{c10::DeviceType::CPU};
+    bool contiguous = false;
+  };
+  std::vector<OutputMeta> output_metas;
+  // tdx::set_data only: the producer `self` had BEFORE the assignment.
+  // set_data swaps the impl's record for the new value's, so by the time
+  // the op is recorded both input slots name the new value's producer;
+  // this is what is left of the old lineage. Weak: it lives on only while
+  // something else (a `to` that read it, say) still depends on it, which
+  // is exactly when it matters.
+  std::weak_ptr<OpNode> set_data_prior;
   std::vector<std::weak_ptr<OpNode>> dependents;
   // The storage families this node writes (weak: groups own nodes, never
   // the reverse). Replay collection closes over each collected writer's
@@ -358,9 +378,12 @@ void recordOp(std::string name,
               torch::jit::Stack& stack,
               size_t rets_begin,
               std::optional<std::pair<uint64_t, uint64_t>> philox =
-                  std::nullopt) {
+                  std::nullopt,
+              std::optional<c10::OperatorHandle> handle = std::nullopt,
+              std::weak_ptr<OpNode> set_data_prior = {}) {
   std::lock_guard<std::recursive_mutex> lock{tape_mutex};
   auto node = std::make_shared<OpNode>();
+  node->set_data_prior = std::move(set_data_prior);
   node->op_nr = next_op_nr.fetch_add(1, std::memory_order_relaxed);
 
   // Input pass: capture producer descriptors for fake args (replacing them
@@ -403,7 +426,7 @@ void recordOp(std::string name,
   }
 
   node->op = RecordedOp{std::move(name), std::move(run), std::move(args),
-                        std::move(tls), philox};
+                        std::move(tls), philox, std::move(handle)};
 
   // Output pass: stamp (or restamp) each fake output's record.
   visitTensors(stack, rets_begin, stack.size(), [&](const at::Tensor& t) {
@@ -411,10 +434,14 @@ void recordOp(std::string name,
     auto* fake = asFake(t);
     if (fake == nullptr) {
       node->output_storages.emplace_back();
+      node->output_metas.emplace_back();
       return;
     }
     const c10::Storage& out_storage = fake->meta_tensor().storage();
     node->output_storages.push_back(out_storage);
+    node->output_metas.push_back(OpNode::OutputMeta{
+        fake->meta_tensor().scalar_type(), fake->fake_device(),
+        fake->meta_tensor().is_contiguous()});
 
     auto rec = getRecord(fake);
     if (rec == nullptr) {
@@ -668,7 +695,7 @@ void deferredInitHandler(const c10::OperatorHandle& op,
           }
           handle.callBoxed(s);
         },
-        std::move(saved), std::move(tls), *stack, rets_begin, philox);
+        std::move(saved), std::move(tls), *stack, rets_begin, philox, op);
   }
 }
 
@@ -841,9 +868,12 @@ void ProxyVariableHooks::set_data(const at::TensorBase& self,
   bool record = shouldRecordHere() && isFake(self_t) &&
                 getRecord(asFake(self_t)) != nullptr;
   std::vector<c10::IValue> args;
+  std::weak_ptr<OpNode> prior;
   if (record) {
     // Capture the pre-mutation producer of `self` before the impl swap.
     args = {c10::IValue{self_t}, c10::IValue{new_t}};
+    std::lock_guard<std::recursive_mutex> lock{tape_mutex};
+    prior = getRecord(asFake(self_t))->desc.node;
   }
   inner_->set_data(self, new_data);
   if (!record) {
@@ -860,7 +890,8 @@ void ProxyVariableHooks::set_data(const at::TensorBase& self,
         slf.set_data(nd);
         s.emplace_back(slf);
       },
-      std::move(args), at::ThreadLocalState{}, rets, 0);
+      std::move(args), at::ThreadLocalState{}, rets, 0, std::nullopt,
+      std::nullopt, std::move(prior));
 }
 
 // ---------------------------------------------------------------------------
@@ -1149,7 +1180,22 @@ struct ChainStep {
     // (uniform_ -> erfinv_ -> mul_ -> add_ -> clamp_) slice-
     // materializable.
     kPointwise,
+    // Out-of-place dtype conversion on the same device (aten::to /
+    // aten::_to_copy, strided, contiguous source): elementwise, so slicing
+    // commutes with it. The steps before it run at `dtype`, the steps
+    // after it at `cast_to`.
+    kCast,
   } kind;
+  // The dtype the step runs at: its output's for everything but kCast,
+  // whose `dtype` is the SOURCE dtype and `cast_to` the result's.
+  c10::ScalarType dtype = c10::ScalarType::Undefined;
+  c10::ScalarType cast_to = c10::ScalarType::Undefined;
+  // The step's result lives in a new storage (kCast, or a same-dtype
+  // copying `to`, which is a kPass): the lineage continues, towards the
+  // factory, in `in_storage`.
+  bool out_of_place = false;
+  c10::Storage in_storage;
+  bool is_set_data = false;
   double p0 = 0.0;  // from / mean / fill value
   double p1 = 0.0;  // to / std
   std::optional<std::pair<uint64_t, uint64_t>> philox;
@@ -1313,6 +1359,98 @@ bool isScalarLikeArg(const c10::IValue& v) {
   return false;
 }
 
+// The op names behind the out-of-place `to` step and the aliasing kPass
+// steps; classifyChainNode and setDataFollowsLineage both go by these.
+bool isToOpName(const std::string& name) {
+  return name == "aten::to" || name == "aten::_to_copy";
+}
+
+bool isAliasPassOpName(const std::string& name) {
+  return name == "aten::detach" || name == "tdx::variable_data" ||
+         name == "aten::alias";
+}
+
+bool isFloat3(c10::ScalarType t) {
+  return t == at::kFloat || t == at::kBFloat16 || t == at::kHalf;
+}
+
+// aten::to (every overload) / aten::_to_copy as a chain step: a kPass when
+// it returned its input or copied it at the same dtype, a kCast when the
+// dtype changed. Anything that moves the data elsewhere or lays it out
+// differently is not a simple chain.
+void classifyToNode(const OpNode& node, ChainStep& step) {
+  const RecordedOp& op = *node.op;
+  auto reject = [&](const char* why) {
+    TORCH_CHECK(false, "slice materialization: `", op.name, "` ", why,
+                " is not a whole-tensor init op; materialize the tensor "
+                "fully instead.");
+  };
+  if (!op.handle.has_value() || node.input_slots.empty() ||
+      !node.input_slots[0].desc.has_value() || node.output_metas.empty() ||
+      !node.output_storages[0]) {
+    reject("recorded without its schema or source");
+  }
+  const auto& schema_args = op.handle->schema().arguments();
+  for (size_t i = 0; i < schema_args.size() && i < op.args.size(); ++i) {
+    const std::string& arg = schema_args[i].name();
+    const c10::IValue& v = op.args[i];
+    if (arg == "layout") {
+      if (!v.isNone() &&
+          !(v.isInt() &&
+            static_cast<c10::Layout>(v.toInt()) == c10::kStrided)) {
+        reject("to a non-strided layout");
+      }
+    } else if (arg == "pin_memory") {
+      if (!v.isNone() && !(v.isBool() && !v.toBool())) {
+        reject("into pinned memory");
+      }
+    } else if (arg == "memory_format") {
+      if (!v.isNone()) {
+        if (!v.isInt()) {
+          reject("to another memory format");
+        }
+        const auto mf = static_cast<c10::MemoryFormat>(v.toInt());
+        if (mf != c10::MemoryFormat::Preserve &&
+            mf != c10::MemoryFormat::Contiguous) {
+          reject("to another memory format");
+        }
+      }
+    } else if (arg == "other") {
+      // to.other: a real tensor only lends its dtype and device; a fake
+      // one (nulled out in the frame) would be a second lineage.
+      if (!v.isTensor() || !v.toTensor().defined() || isFake(v.toTensor())) {
+        reject("to the dtype of another deferred tensor");
+      }
+    }
+  }
+  const OpOutputDescriptor& src = *node.input_slots[0].desc;
+  if (src.index >= src.node->output_metas.size()) {
+    reject("of a source recorded without metadata");
+  }
+  const OpNode::OutputMeta& in = src.node->output_metas[src.index];
+  const OpNode::OutputMeta& out = node.output_metas[0];
+  if (in.device != out.device) {
+    reject("to another device");
+  }
+  if (!in.contiguous || !out.contiguous) {
+    reject("of a non-contiguous tensor");
+  }
+  step.dtype = in.dtype;
+  const c10::Storage& in_storage = src.node->output_storages[src.index];
+  if (storagesAlias(node.output_storages[0], in_storage)) {
+    step.kind = ChainStep::Kind::kPass;  // nothing to convert: returned self
+    return;
+  }
+  step.out_of_place = true;
+  step.in_storage = in_storage;
+  if (in.dtype == out.dtype) {
+    step.kind = ChainStep::Kind::kPass;  // copy=True
+    return;
+  }
+  step.kind = ChainStep::Kind::kCast;
+  step.cast_to = out.dtype;
+}
+
 ChainStep classifyChainNode(const OpNode& node) {
   TORCH_CHECK(node.op.has_value(),
               "slice materialization: the tape segment for `",
@@ -1335,7 +1473,18 @@ ChainStep classifyChainNode(const OpNode& node) {
     TORCH_CHECK(false, "slice materialization: unexpected argument type `",
                 v.tagKind(), "` in `", op.name, "`");
   };
-  if (chainNameIs(op.name, "aten::empty")) {
+  if (!node.output_metas.empty()) {
+    step.dtype = node.output_metas[0].dtype;
+  }
+  if (isToOpName(op.name)) {
+    classifyToNode(node, step);
+  } else if (op.name == "tdx::set_data") {
+    // `p.data = t`: p continues t's lineage. Whether t is this lineage's
+    // own latest value is checked where the whole chain is known
+    // (buildChainSteps).
+    step.kind = ChainStep::Kind::kPass;
+    step.is_set_data = true;
+  } else if (chainNameIs(op.name, "aten::empty")) {
     step.kind = ChainStep::Kind::kFactory;
   } else if (chainNameIs(op.name, "aten::zeros")) {
     step.kind = ChainStep::Kind::kZero;
@@ -1369,8 +1518,7 @@ ChainStep classifyChainNode(const OpNode& node) {
     step.p0 = scalarArg(1);
   } else if (op.name == "aten::zero_") {
     step.kind = ChainStep::Kind::kZero;
-  } else if (op.name == "aten::detach" || op.name == "tdx::variable_data" ||
-             op.name == "aten::alias") {
+  } else if (isAliasPassOpName(op.name)) {
     step.kind = ChainStep::Kind::kPass;
   } else if (isPointwiseScalarOpName(op.name) &&
              std::all_of(op.args.begin() + 1, op.args.end(),
@@ -1441,6 +1589,10 @@ void applyShardStep(const ChainStep& step, at::Tensor& shard,
   switch (step.kind) {
     case ChainStep::Kind::kFactory:
     case ChainStep::Kind::kPass:
+      return;
+    case ChainStep::Kind::kCast:
+      // Replaces the shard; replayChainOnShard splits the chain there.
+      TORCH_INTERNAL_ASSERT(false, "kCast is not an in-place shard step");
       return;
     case ChainStep::Kind::kPointwise: {
       torch::jit::Stack s;
@@ -1564,6 +1716,57 @@ void applyFusedShardStep(const ChainStep& rng, const std::vector<TailOp>& tail,
                        static_cast<int64_t>(rng.philox->second));
 }
 
+// applyFusedShardStep for a chain that ends in a conversion: `shard` has
+// the FINAL dtype, the values are drawn (and the tail applied) at
+// `src_dtype`. Windows only; boxes convert a temporary (replayChainOnShard).
+void applyFusedCastShardStep(const ChainStep& rng,
+                             const std::vector<TailOp>& tail,
+                             c10::ScalarType src_dtype, at::Tensor& shard,
+                             const ShardWindow& w, int64_t full_numel) {
+  TORCH_CHECK(rng.philox.has_value(),
+              "slice materialization: this RNG op carries no pinned "
+              "Philox state (was it recorded by an older build?)");
+  static const auto chain_cast_shard_win =
+      c10::Dispatcher::singleton()
+          .findSchemaOrThrow("tdx::rng_chain_cast_shard_win_", "")
+          .typed<at::Tensor&(at::Tensor&, at::ScalarType, int64_t, int64_t,
+                             int64_t, int64_t, int64_t, double, double,
+                             at::IntArrayRef, at::ArrayRef<double>,
+                             at::ArrayRef<double>, int64_t, int64_t,
+                             int64_t)>();
+  std::vector<int64_t> ops;
+  std::vector<double> s0;
+  std::vector<double> s1;
+  for (const TailOp& t : tail) {
+    ops.push_back(t.op);
+    s0.push_back(t.s0);
+    s1.push_back(t.s1);
+  }
+  chain_cast_shard_win.call(shard, src_dtype, w.n_blocks, w.block_len,
+                            w.g_stride, w.g_off, rngDistCode(rng.kind),
+                            rng.p0, rng.p1, ops, s0, s1, full_numel,
+                            static_cast<int64_t>(rng.philox->first),
+                            static_cast<int64_t>(rng.philox->second));
+}
+
+// The shard converted to `dtype`: tdx::copy_ (bitwise ATen's conversion)
+// between two of {f32, bf16, f16}, ATen's `to` for anything else (an fp8
+// destination, a double source).
+at::Tensor castShard(const at::Tensor& shard, c10::ScalarType dtype) {
+  c10::impl::ExcludeDispatchKeyGuard no_deferred{kDeferredKey};
+  c10::impl::ExcludeDispatchKeyGuard no_fake{kFakeKey};
+  if (!isFloat3(shard.scalar_type()) || !isFloat3(dtype)) {
+    return shard.to(dtype);
+  }
+  static const auto copy =
+      c10::Dispatcher::singleton()
+          .findSchemaOrThrow("tdx::copy_", "")
+          .typed<at::Tensor&(at::Tensor&, const at::Tensor&, bool)>();
+  at::Tensor out = at::empty(shard.sizes(), shard.options().dtype(dtype));
+  copy.call(out, shard, false);
+  return out;
+}
+
 // Whether `op` on a tensor of `dtype` and `numel` elements may fuse in
 // the current switch state: everything in the fusable set, except the
 // steps that are NOT bitwise equal to ATen's kernels on gfx950, which
@@ -1589,33 +1792,176 @@ bool isRngStep(const ChainStep& step) {
          step.kind == ChainStep::Kind::kBernoulli;
 }
 
-// Index of the RNG step of a trailing run [RNG step, fusable tail...,
-// pass steps...] that one fused launch can serve, or nullopt when the
-// chain does not end that way.
-std::optional<size_t> fusedRunStart(const std::vector<ChainStep>& steps,
-                                    c10::ScalarType dtype, int64_t numel) {
-  if (!fusedInitChainsEnabled() ||
-      (dtype != at::kFloat && dtype != at::kBFloat16 && dtype != at::kHalf)) {
+// `p.data = t` keeps a chain simple only when t is this lineage's own
+// latest value: walking back from t's producer through conversions and
+// aliasing pass-throughs (producer edges, not tape positions) must arrive
+// at the producer p had before it was assigned (OpNode::set_data_prior),
+// and nothing but pass steps may sit between t's producer and the
+// assignment. After `p.data = other` p shares other's record, so without
+// this check it would silently plan and slice as other's lineage.
+bool setDataFollowsLineage(const std::vector<std::shared_ptr<OpNode>>& nodes,
+                           const std::vector<ChainStep>& steps, size_t i) {
+  const OpNode& node = *nodes[i];
+  const std::shared_ptr<OpNode> prior = node.set_data_prior.lock();
+  if (prior == nullptr || node.input_slots.size() != 2 ||
+      !node.input_slots[1].desc.has_value()) {
+    return false;
+  }
+  const OpNode* self_producer = prior.get();
+  const OpNode* data_producer = node.input_slots[1].desc->node.get();
+  size_t at = i;
+  while (at > 0 && nodes[at - 1].get() != data_producer) {
+    --at;
+    if (steps[at].kind != ChainStep::Kind::kPass || steps[at].out_of_place) {
+      return false;
+    }
+  }
+  if (at == 0) {
+    return false;
+  }
+  // A producer is always recorded before its consumer, so op_nr falls
+  // with every hop and the walk ends at, or passes, self_producer.
+  const OpNode* cur = data_producer;
+  while (cur != self_producer) {
+    if (cur->op_nr < self_producer->op_nr || !cur->op.has_value() ||
+        !(isToOpName(cur->op->name) || isAliasPassOpName(cur->op->name)) ||
+        cur->input_slots.empty() || !cur->input_slots[0].desc.has_value()) {
+      return false;
+    }
+    cur = cur->input_slots[0].desc->node.get();
+  }
+  return true;
+}
+
+// The tensor's replay set as chain steps, in tape order, reduced to its
+// own lineage. Throws (c10::Error, "slice materialization: ...") when the
+// tape is not a simple init chain.
+//
+// Until a conversion enters the picture every step acts on one storage
+// and the replay set IS the lineage. A `to` makes a second storage: the
+// walk goes backwards from the final tensor's storage, crosses a
+// conversion into its source's storage, and drops conversions that
+// produced some OTHER tensor (the replay set pulls in `h = p.half()` when
+// p is overwritten afterwards; h is no part of p).
+std::vector<ChainStep> buildChainSteps(const TensorRecord& rec,
+                                       const c10::Storage& final_storage) {
+  auto nodes = buildCallStack(rec);
+  std::vector<ChainStep> all;
+  all.reserve(nodes.size());
+  for (const auto& n : nodes) {
+    all.push_back(classifyChainNode(*n));
+  }
+  std::vector<char> keep(all.size(), 1);
+  std::vector<char> in_lineage(all.size(), 1);
+  bool crosses = false;
+  c10::Storage cur = final_storage;
+  for (size_t i = all.size(); i-- > 0;) {
+    const bool in = outputsAlias(*nodes[i], cur);
+    in_lineage[i] = in;
+    if (all[i].out_of_place) {
+      if (!in) {
+        keep[i] = 0;
+        continue;
+      }
+      crosses = true;
+      cur = all[i].in_storage;
+    } else if (all[i].is_set_data) {
+      TORCH_CHECK(in && setDataFollowsLineage(nodes, all, i),
+                  "slice materialization: `tdx::set_data` assigns a tensor "
+                  "of another lineage, which is not a whole-tensor init op; "
+                  "materialize the tensor fully instead.");
+    }
+  }
+  std::vector<ChainStep> steps;
+  steps.reserve(all.size());
+  for (size_t i = 0; i < all.size(); ++i) {
+    if (!keep[i]) {
+      continue;
+    }
+    TORCH_CHECK(!crosses || in_lineage[i],
+                "slice materialization: the tape mixes a dtype conversion "
+                "with ops on another tensor; materialize the tensor fully "
+                "instead.");
+    steps.push_back(std::move(all[i]));
+  }
+  return steps;
+}
+
+// A trailing run [RNG step, fusable tail..., pass steps...] of
+// steps[lo, hi) that one fused launch can serve. With `allow_cast` the
+// run may also hold exactly one kCast between two of {f32, bf16, f16}
+// behind the tail (pass steps on either side of it), and the tail may
+// then be empty: that is one launch of tdx::rng_chain_cast_shard_win_.
+// The tail rules are evaluated at the dtype the tail runs at — the
+// cast's SOURCE dtype.
+struct FusedRun {
+  size_t rng;         // index of the RNG step
+  size_t tail_begin;  // [tail_begin, tail_end): the kPointwise steps
+  size_t tail_end;
+  std::optional<size_t> cast;
+};
+
+std::optional<FusedRun> fusedRunStart(const std::vector<ChainStep>& steps,
+                                      size_t lo, size_t hi, int64_t numel,
+                                      bool allow_cast) {
+  if (!fusedInitChainsEnabled()) {
     return std::nullopt;
   }
-  size_t end = steps.size();
-  while (end > 0 && steps[end - 1].kind == ChainStep::Kind::kPass) {
+  size_t end = hi;
+  while (end > lo && steps[end - 1].kind == ChainStep::Kind::kPass) {
     --end;
   }
+  std::optional<size_t> cast;
+  if (allow_cast && end > lo &&
+      steps[end - 1].kind == ChainStep::Kind::kCast) {
+    cast = --end;
+    if (!isFloat3(steps[*cast].cast_to)) {
+      return std::nullopt;
+    }
+    while (end > lo && steps[end - 1].kind == ChainStep::Kind::kPass) {
+      --end;
+    }
+  }
+  if (end == lo) {
+    return std::nullopt;
+  }
+  const c10::ScalarType dtype = steps[end - 1].dtype;
+  if (!isFloat3(dtype)) {
+    return std::nullopt;
+  }
   size_t first_tail = end;
-  while (first_tail > 0 &&
+  while (first_tail > lo &&
          steps[first_tail - 1].kind == ChainStep::Kind::kPointwise &&
          steps[first_tail - 1].tail_op.has_value() &&
          tailOpAdmitted(*steps[first_tail - 1].tail_op, dtype, numel)) {
     --first_tail;
   }
   const size_t n_tail = end - first_tail;
-  if (n_tail == 0 || n_tail > kMaxTailOps || first_tail == 0 ||
-      !isRngStep(steps[first_tail - 1]) ||
+  if ((n_tail == 0 && !cast.has_value()) || n_tail > kMaxTailOps ||
+      first_tail == lo || !isRngStep(steps[first_tail - 1]) ||
       !steps[first_tail - 1].philox.has_value()) {
     return std::nullopt;
   }
-  return first_tail - 1;
+  return FusedRun{first_tail - 1, first_tail, end, cast};
+}
+
+// double -> `dtype` -> double, the way tdx::fill_ / ATen narrow a Scalar
+// into a tensor of that dtype (through float for the 16-bit types).
+std::optional<double> roundScalarThrough(double v, c10::ScalarType dtype) {
+  switch (dtype) {
+    case at::kDouble:
+      return v;
+    case at::kFloat:
+      return static_cast<double>(static_cast<float>(v));
+    case at::kBFloat16:
+      return static_cast<double>(
+          static_cast<float>(c10::BFloat16(static_cast<float>(v))));
+    case at::kHalf:
+      return static_cast<double>(
+          static_cast<float>(c10::Half(static_cast<float>(v))));
+    default:
+      return std::nullopt;
+  }
 }
 
 // Shared body of tensorInitPlan (allow_tail == false) and tensorChainPlan.
@@ -1636,22 +1982,31 @@ std::optional<ChainPlan> chainPlanImpl(const at::Tensor& tensor,
   std::lock_guard<std::recursive_mutex> lock{tape_mutex};
   ChainPlan plan;
   try {
-    auto nodes = buildCallStack(*rec);
+    const std::vector<ChainStep> steps =
+        buildChainSteps(*rec, meta.storage());
     bool have_value = false;
     bool tail_unfusable = false;  // a live pointwise step we cannot fuse
-    for (const auto& n : nodes) {
-      ChainStep step = classifyChainNode(*n);
+    // At most one conversion, and nothing that changes values behind it:
+    // the kernels generate at one dtype and store at another, once.
+    std::optional<c10::ScalarType> cast_src;
+    for (const ChainStep& step : steps) {
+      if (cast_src.has_value() && step.kind != ChainStep::Kind::kPass &&
+          step.kind != ChainStep::Kind::kFactory) {
+        return std::nullopt;
+      }
       switch (step.kind) {
         case ChainStep::Kind::kFactory:
         case ChainStep::Kind::kPass:
+          break;
+        case ChainStep::Kind::kCast:
+          cast_src = step.dtype;
           break;
         case ChainStep::Kind::kPointwise:
           if (!allow_tail) {
             return std::nullopt;  // needs sequential application
           }
           if (step.tail_op.has_value() &&
-              tailOpAdmitted(*step.tail_op, meta.scalar_type(),
-                             meta.numel())) {
+              tailOpAdmitted(*step.tail_op, step.dtype, meta.numel())) {
             plan.tail.push_back(*step.tail_op);
           } else {
             tail_unfusable = true;
@@ -1704,6 +2059,33 @@ std::optional<ChainPlan> chainPlanImpl(const at::Tensor& tensor,
         return std::nullopt;
       }
     }
+    if (cast_src.has_value()) {
+      switch (plan.kind) {
+        case InitPlan::Kind::kUniform:
+        case InitPlan::Kind::kNormal:
+        case InitPlan::Kind::kBernoulli:
+          // The values depend on the dtype they were drawn at (group
+          // size, tail arithmetic): the cast kernels take both dtypes.
+          if (!isFloat3(*cast_src) || !isFloat3(meta.scalar_type())) {
+            return std::nullopt;
+          }
+          plan.src_dtype = *cast_src;
+          break;
+        case InitPlan::Kind::kFill: {
+          // A constant converts on the host: a plain fill at the final
+          // dtype with the value as the source tensor held it.
+          auto rounded = roundScalarThrough(plan.p0, *cast_src);
+          if (!rounded.has_value()) {
+            return std::nullopt;
+          }
+          plan.p0 = *rounded;
+          break;
+        }
+        case InitPlan::Kind::kZero:
+        case InitPlan::Kind::kFactory:
+          break;
+      }
+    }
   } catch (const c10::Error&) {
     return std::nullopt;  // not a simple chain
   }
@@ -1722,39 +2104,66 @@ at::Tensor replayChainOnShard(FakeTensorImpl* fake,
   const at::Tensor& meta = fake->meta_tensor();
   std::lock_guard<std::recursive_mutex> lock{tape_mutex};
   auto rec = getRecord(fake);
-  auto nodes = buildCallStack(*rec);
-  std::vector<ChainStep> steps;
-  steps.reserve(nodes.size());
-  for (const auto& n : nodes) {
-    steps.push_back(classifyChainNode(*n));
-  }
+  const std::vector<ChainStep> steps = buildChainSteps(*rec, meta.storage());
   TORCH_CHECK(!steps.empty() &&
                   (steps.front().kind == ChainStep::Kind::kFactory ||
                    steps.front().kind == ChainStep::Kind::kZero ||
                    steps.front().kind == ChainStep::Kind::kFill),
               "slice materialization: the tape does not start with a "
               "factory op");
-
-  at::Tensor shard = at::empty(
-      shard_sizes, at::TensorOptions()
-                       .dtype(meta.scalar_type())
-                       .device(fake->fake_device()));
-  // A trailing [RNG step, fusable tail...] run is one fused launch; any
-  // other arrangement applies step by step.
-  const std::optional<size_t> fused_at =
-      fusedRunStart(steps, meta.scalar_type(), meta.numel());
-  for (size_t i = 0; i < steps.size(); ++i) {
-    if (fused_at.has_value() && i == *fused_at) {
-      std::vector<TailOp> tail;
-      for (++i; i < steps.size() &&
-                steps[i].kind == ChainStep::Kind::kPointwise;
-           ++i) {
-        tail.push_back(*steps[i].tail_op);
-      }
-      applyFusedShardStep(steps[*fused_at], tail, shard, w, meta.numel());
-      break;  // only pass steps remain
+  const auto options = at::TensorOptions().device(fake->fake_device());
+  auto tailOf = [&](const FusedRun& run) {
+    std::vector<TailOp> tail;
+    for (size_t i = run.tail_begin; i < run.tail_end; ++i) {
+      tail.push_back(*steps[i].tail_op);
     }
-    applyShardStep(steps[i], shard, w, meta.numel());
+    return tail;
+  };
+
+  // [RNG step, tail..., one cast] at the end of the chain is one launch
+  // that draws at the source dtype and stores the final one; everything
+  // before the RNG step is overwritten by it. A box of two or more levels
+  // has no cast kernel: it takes the segments below (the box op at the
+  // source dtype into a block-sized temporary, then the conversion).
+  if (!w.box.has_value()) {
+    const auto run = fusedRunStart(steps, 0, steps.size(), meta.numel(),
+                                   /*allow_cast=*/true);
+    if (run.has_value() && run->cast.has_value()) {
+      at::Tensor shard =
+          at::empty(shard_sizes, options.dtype(steps[*run->cast].cast_to));
+      applyFusedCastShardStep(steps[run->rng], tailOf(*run),
+                              steps[*run->cast].dtype, shard, w,
+                              meta.numel());
+      return shard;
+    }
+  }
+
+  // Otherwise the chain runs in segments of one dtype each, split at its
+  // conversions. The shard starts at the chain's FIRST dtype; within a
+  // segment a trailing [RNG step, fusable tail...] run is one fused
+  // launch and any other arrangement applies step by step; a conversion
+  // replaces the shard by its converted copy. Only shard-sized tensors
+  // exist at any point.
+  at::Tensor shard = at::empty(shard_sizes, options.dtype(steps.front().dtype));
+  size_t lo = 0;
+  while (lo < steps.size()) {
+    size_t hi = lo;
+    while (hi < steps.size() && steps[hi].kind != ChainStep::Kind::kCast) {
+      ++hi;
+    }
+    const auto run =
+        fusedRunStart(steps, lo, hi, meta.numel(), /*allow_cast=*/false);
+    for (size_t i = lo; i < hi; ++i) {
+      if (run.has_value() && i == run->rng) {
+        applyFusedShardStep(steps[i], tailOf(*run), shard, w, meta.numel());
+        break;  // only pass steps remain in this segment
+      }
+      applyShardStep(steps[i], shard, w, meta.numel());
+    }
+    if (hi < steps.size()) {
+      shard = castShard(shard, steps[hi].cast_to);
+    }
+    lo = hi + 1;
   }
   return shard;
 }

@@ -67,6 +67,14 @@ struct InitPlan {
   uint64_t offset = 0;
   std::vector<int64_t> sizes;
   c10::ScalarType dtype = c10::ScalarType::Float;
+  // Set when the chain ends in a dtype conversion behind an RNG value
+  // step (`empty(..).normal_().to(bf16)`, `Module.to(dtype)` in the
+  // builder): the values are drawn, and the tail applied, at src_dtype and
+  // stored as `dtype` (tdx::rng_chain_cast_). Both are then one of
+  // float32/bf16/f16. A converted fill/zero is a plain fill at `dtype`
+  // with p0 already rounded through the source dtype, and has no
+  // src_dtype.
+  std::optional<c10::ScalarType> src_dtype;
   c10::Device device{c10::DeviceType::CPU};
   bool requires_grad = false;
 };
@@ -123,12 +131,16 @@ std::optional<ChainPlan> tensorChainPlan(const at::Tensor& tensor);
 // weights; dim 1 serves row-parallel (Megatron-style TP) weights.
 // Requires the tensor's tape to be a "simple init chain" — a factory
 // (empty/zeros/ones/full) followed by whole-tensor in-place init ops
-// (uniform_/normal_/fill_/zero_) and aliasing pass-throughs
-// (detach/variable_data) — which is exactly what module constructors
-// record; throws a descriptive error otherwise so callers can fall back
-// to full materialization. This is the FSDP/TP init primitive: N ranks
-// materialize disjoint slices of a model larger than any single device,
-// with zero communication.
+// (uniform_/normal_/fill_/zero_), aliasing pass-throughs
+// (detach/variable_data) and same-device dtype conversions (`to`, and
+// the `p.data = p.to(dtype)` that `Module.to(dtype)` records) — which is
+// exactly what module constructors record; throws a descriptive error
+// otherwise so callers can fall back to full materialization. The shard
+// is generated at the chain's first dtype and converted shard-sized; an
+// RNG step (and fusable tail) followed by one conversion between
+// float32/bf16/f16 is a single launch that stores the final dtype. This
+// is the FSDP/TP init primitive: N ranks materialize disjoint slices of a
+// model larger than any single device, with zero communication.
 at::Tensor materializeTensorShard(const at::Tensor& tensor,
                                   int64_t start_row,
                                   int64_t end_row,

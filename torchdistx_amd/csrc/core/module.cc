@@ -34,6 +34,15 @@ void enterFakeModeBinding(bool fake_cuda) {
   tdx::enterFakeMode(fake_cuda);
 }
 
+// InitPlan::src_dtype for the plan dicts: None unless the chain ends in a
+// dtype conversion behind an RNG step.
+pybind11::object srcDtypeObject(const tdx::InitPlan& plan) {
+  if (!plan.src_dtype.has_value()) {
+    return pybind11::none();
+  }
+  return pybind11::cast(*plan.src_dtype);
+}
+
 void leaveFakeModeBinding() {
   tdx::leaveFakeMode();
   if (!tdx::isFakeModeActive() && fake_cuda_lazy_init_suppressions > 0) {
@@ -127,11 +136,14 @@ PYBIND11_MODULE(_C, m) {
     d["offset"] = static_cast<int64_t>(plan->offset);
     d["sizes"] = plan->sizes;
     d["dtype"] = pybind11::cast(plan->dtype);
+    d["src_dtype"] = srcDtypeObject(*plan);
     d["device"] = pybind11::cast(plan->device);
     d["requires_grad"] = plan->requires_grad;
     return d;
   }, "Reduced replay plan of a simple init chain (the final whole-tensor "
-     "value step), or None when the tape is not that simple. Feeds the "
+     "value step), or None when the tape is not that simple. \"dtype\" is "
+     "the final dtype; \"src_dtype\" is the dtype an RNG step was recorded "
+     "at when a conversion follows it, else None. Feeds the "
      "batched replay planner (materialize_module_batched).");
 
   m.def("set_fused_init_chains", &tdx::setFusedInitChains,
@@ -160,6 +172,7 @@ PYBIND11_MODULE(_C, m) {
     d["offset"] = static_cast<int64_t>(plan->offset);
     d["sizes"] = plan->sizes;
     d["dtype"] = pybind11::cast(plan->dtype);
+    d["src_dtype"] = srcDtypeObject(*plan);
     d["device"] = pybind11::cast(plan->device);
     d["requires_grad"] = plan->requires_grad;
     pybind11::list tail;

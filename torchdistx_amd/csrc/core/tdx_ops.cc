@@ -498,6 +498,50 @@ at::Tensor& cpu_rng_chain_(at::Tensor& self, int64_t dist, double p0,
                                   self.numel(), seed, offset);
 }
 
+// ---- RNG + tail + dtype conversion ----------------------------------------
+// The element is what rng_chain_ gives at src_dtype (source-dtype Philox
+// group, value rounded through src_dtype, tail at src_dtype), converted
+// to the shard's dtype. CPU form: exactly that, through a shard-sized
+// temporary at src_dtype; the CDNA4 kernels keep the value in registers
+// (csrc/hip/init_kernels.hip rng_chain_cast_window_kernel).
+
+bool isCastChainDtype(c10::ScalarType t) {
+  return t == at::kFloat || t == at::kBFloat16 || t == at::kHalf;
+}
+
+at::Tensor& cpu_rng_chain_cast_shard_win_(
+    at::Tensor& shard, at::ScalarType src_dtype, int64_t n_blocks,
+    int64_t block_len, int64_t g_stride, int64_t g_off, int64_t dist,
+    double p0, double p1, at::IntArrayRef tail_ops,
+    at::ArrayRef<double> tail_s0, at::ArrayRef<double> tail_s1,
+    int64_t full_numel, int64_t seed, int64_t offset) {
+  TORCH_CHECK(isCastChainDtype(src_dtype) &&
+                  isCastChainDtype(shard.scalar_type()) &&
+                  src_dtype != shard.scalar_type(),
+              "rng_chain_cast: two different dtypes of float32/bf16/fp16, "
+              "got ", src_dtype, " -> ", shard.scalar_type());
+  TORCH_CHECK(shard.is_contiguous(),
+              "tdx CPU init requires contiguous tensors");
+  at::Tensor src = at::empty(shard.sizes(), shard.options().dtype(src_dtype));
+  cpu_rng_chain_shard_win_(src, n_blocks, block_len, g_stride, g_off, dist,
+                           p0, p1, tail_ops, tail_s0, tail_s1, full_numel,
+                           seed, offset);
+  shard.copy_(src);
+  return shard;
+}
+
+at::Tensor& cpu_rng_chain_cast_(at::Tensor& self, at::ScalarType src_dtype,
+                                int64_t dist, double p0, double p1,
+                                at::IntArrayRef tail_ops,
+                                at::ArrayRef<double> tail_s0,
+                                at::ArrayRef<double> tail_s1, int64_t seed,
+                                int64_t offset) {
+  return cpu_rng_chain_cast_shard_win_(self, src_dtype, 1, self.numel(),
+                                       self.numel(), 0, dist, p0, p1,
+                                       tail_ops, tail_s0, tail_s1,
+                                       self.numel(), seed, offset);
+}
+
 TORCH_LIBRARY(tdx, m) {
   m.def(
       "uniform_(Tensor(a!) self, float from=0., float to=1., *, "
@@ -550,6 +594,19 @@ TORCH_LIBRARY(tdx, m) {
       "int g_stride, int g_off, int dist, float p0, float p1, "
       "int[] tail_ops, float[] tail_s0, float[] tail_s1, int full_numel, "
       "*, int seed, int offset) -> Tensor(a!)");
+  // rng_chain_ / rng_chain_shard_win_ drawn (and the tail applied) at
+  // src_dtype, stored in the tensor's own, different dtype; both are one
+  // of float32/bf16/fp16. Bitwise the src_dtype op followed by `.to()`.
+  m.def(
+      "rng_chain_cast_(Tensor(a!) self, ScalarType src_dtype, int dist, "
+      "float p0, float p1, int[] tail_ops, float[] tail_s0, "
+      "float[] tail_s1, *, int seed, int offset) -> Tensor(a!)");
+  m.def(
+      "rng_chain_cast_shard_win_(Tensor(a!) shard, ScalarType src_dtype, "
+      "int n_blocks, int block_len, int g_stride, int g_off, int dist, "
+      "float p0, float p1, int[] tail_ops, float[] tail_s0, "
+      "float[] tail_s1, int full_numel, *, int seed, int offset) "
+      "-> Tensor(a!)");
   // An N-d box of the full tensor in normalized form (box_geometry.h):
   // extents/g_strides per level, outermost first. Empty tail lists mean
   // no tail.
@@ -576,6 +633,8 @@ TORCH_LIBRARY_IMPL(tdx, CPU, m) {
   m.impl("rng_chain_", cpu_rng_chain_);
   m.impl("rng_chain_shard_win_", cpu_rng_chain_shard_win_);
   m.impl("rng_box_", cpu_rng_box_);
+  m.impl("rng_chain_cast_", cpu_rng_chain_cast_);
+  m.impl("rng_chain_cast_shard_win_", cpu_rng_chain_cast_shard_win_);
 }
 
 }  // namespace

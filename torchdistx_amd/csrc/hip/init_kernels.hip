@@ -1100,6 +1100,400 @@ at::Tensor& tdx_rng_chain_(at::Tensor& self, int64_t dist, double p0,
 }
 
 // ---------------------------------------------------------------------------
+// Chains that end in a dtype conversion (`empty(..).normal_().to(bf16)`,
+// `Module.to(dtype)` inside the builder): the values are drawn, rounded and
+// run through the tail at the SOURCE dtype TSrc, exactly as
+// rng_chain_window_kernel<TSrc> computes them, and stored as TDst — one
+// launch and one store per element, instead of a TSrc tensor written, read
+// back and converted.
+//
+// The two dtypes differ, so at least one is 16-bit and the work unit is 8
+// elements whichever side that is:
+//   * f32 source: TWO consecutive Philox groups (2u, 2u + 1) of 4 values
+//     each make one 16-byte store;
+//   * 16-bit source, f32 destination: one group, 32 bytes, two 16-byte
+//     stores;
+//   * bf16 <-> f16: one group, one 16-byte store.
+// ---------------------------------------------------------------------------
+
+constexpr int kCastUnit = 8;
+
+// The 8 final (float) values of global unit `u`: elements [8u, 8u + 8) of
+// the full tensor, after the tail, as TSrc holds them.
+template <typename TSrc, Dist kDist>
+__device__ __forceinline__ void castUnitValues(uint64_t u, float a, float b,
+                                               uint64_t seed, uint64_t offset,
+                                               const TailProgram& prog,
+                                               float (&vals)[kCastUnit]) {
+  constexpr int kSrcElems = VecTraits<TSrc>::kElems;
+  if constexpr (kSrcElems == kCastUnit) {
+    rngGroupValues<TSrc, kDist>(u, a, b, seed, offset, vals);
+    applyTail<TSrc, kCastUnit>(vals, prog, u * kCastUnit);
+  } else {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      float half_vals[kSrcElems];
+      const uint64_t g = 2 * u + h;
+      rngGroupValues<TSrc, kDist>(g, a, b, seed, offset, half_vals);
+      applyTail<TSrc, kSrcElems>(half_vals, prog, g * kSrcElems);
+#pragma unroll
+      for (int e = 0; e < kSrcElems; ++e) {
+        vals[h * kSrcElems + e] = half_vals[e];
+      }
+    }
+  }
+}
+
+// One element by its global index, for the paths that store elementwise.
+// It draws the element's whole source group and runs the whole tail to
+// keep one value, as rng_chain_window_kernel's elementwise path does: 4x
+// (f32 source) or 8x the RNG and tail work of the vector path per stored
+// element. That is the price of every window with an odd geometry, a
+// misaligned destination or g_off % 8 == 4; it has not been measured.
+template <typename TSrc, typename TDst, Dist kDist>
+__device__ __forceinline__ TDst castElementValue(uint64_t ge, float a,
+                                                 float b, uint64_t seed,
+                                                 uint64_t offset,
+                                                 const TailProgram& prog) {
+  constexpr int kSrcElems = VecTraits<TSrc>::kElems;
+  const uint64_t g = ge / kSrcElems;
+  float vals[kSrcElems];
+  rngGroupValues<TSrc, kDist>(g, a, b, seed, offset, vals);
+  applyTail<TSrc, kSrcElems>(vals, prog, g * kSrcElems);
+  // A select chain, not vals[lane]: a run-time index would put the array
+  // in scratch.
+  const uint32_t lane = static_cast<uint32_t>(ge - g * kSrcElems);
+  float v = vals[0];
+#pragma unroll
+  for (int e = 1; e < kSrcElems; ++e) {
+    v = lane == static_cast<uint32_t>(e) ? vals[e] : v;
+  }
+  return from_float<TDst>(v);
+}
+
+// The first `n` (1..7) elements of global unit `u`, stored elementwise at
+// `p`: the one partial last unit of a single block or of a tensor.
+template <typename TSrc, typename TDst, Dist kDist>
+__device__ __forceinline__ void storePartialCastUnit(
+    TDst* __restrict__ p, uint32_t n, uint64_t u, float a, float b,
+    uint64_t seed, uint64_t offset, const TailProgram& prog) {
+  float vals[kCastUnit];
+  castUnitValues<TSrc, kDist>(u, a, b, seed, offset, prog, vals);
+#pragma unroll
+  for (int e = 0; e < kCastUnit - 1; ++e) {
+    if (static_cast<uint32_t>(e) < n) {
+      p[e] = from_float<TDst>(vals[e]);
+    }
+  }
+}
+
+// Stores the finished unit at `p` (16-byte aligned): one 16-byte store for
+// a 16-bit destination, two for f32.
+template <typename TDst>
+__device__ __forceinline__ void storeCastUnit(TDst* __restrict__ p,
+                                              const float (&vals)[kCastUnit]) {
+  if constexpr (std::is_same_v<TDst, float>) {
+    float4 lo, hi;
+    lo.x = from_float<float>(vals[0]);
+    lo.y = from_float<float>(vals[1]);
+    lo.z = from_float<float>(vals[2]);
+    lo.w = from_float<float>(vals[3]);
+    hi.x = from_float<float>(vals[4]);
+    hi.y = from_float<float>(vals[5]);
+    hi.z = from_float<float>(vals[6]);
+    hi.w = from_float<float>(vals[7]);
+    reinterpret_cast<float4*>(p)[0] = lo;
+    reinterpret_cast<float4*>(p)[1] = hi;
+  } else {
+    typename VecTraits<TDst>::Vec v;
+    TDst* vp = reinterpret_cast<TDst*>(&v);
+#pragma unroll
+    for (int e = 0; e < kCastUnit; ++e) {
+      vp[e] = from_float<TDst>(vals[e]);
+    }
+    *reinterpret_cast<typename VecTraits<TDst>::Vec*>(p) = v;
+  }
+}
+
+// The vector loop shared by the window and the batched kernel: this thread
+// takes shard units j0, j0 + stride, ... below n_units; unit j is stored at
+// out + 8 j and holds global unit gunit(j). The block is 1-d with a
+// multiple of 64 threads and j0 - lane is a multiple of 64, so the 64
+// lanes of a wave always hold 64 consecutive shard units (a "chunk").
+//
+// f32 destination: a lane's unit is 32 bytes, and two plain 16-byte stores
+// per lane would each touch every other 16 bytes of 2 KiB. While a whole
+// chunk lies below n_units (a wave-uniform test, so all 64 lanes are
+// active) the lanes pair up instead: lane 2k takes unit k of the chunk,
+// lane 2k + 1 unit 32 + k, the pair swaps one half each (even lane: its
+// upper half for the odd lane's lower half), and then the first store of
+// the wave writes units 0..31 of the chunk and the second units 32..63 —
+// lane l at byte 16 l of a contiguous 1 KiB both times. The values do not
+// depend on which lane computes them.
+template <typename TSrc, typename TDst, Dist kDist, typename IdxT,
+          typename GlobalUnitFn>
+__device__ __forceinline__ void castUnitLoop(TDst* __restrict__ out, IdxT j0,
+                                             IdxT n_units, IdxT stride,
+                                             GlobalUnitFn gunit, float a,
+                                             float b, uint64_t seed,
+                                             uint64_t offset,
+                                             const TailProgram& prog) {
+  const uint32_t lane = threadIdx.x & 63u;
+  for (IdxT j = j0; j < n_units; j += stride) {
+    float vals[kCastUnit];
+    if constexpr (std::is_same_v<TDst, float>) {
+      const IdxT chunk = j - static_cast<IdxT>(lane);
+      if (chunk + 64 <= n_units) {
+        const uint32_t odd = lane & 1u;
+        const IdxT mine = chunk + static_cast<IdxT>((lane >> 1) + (odd << 5));
+        castUnitValues<TSrc, kDist>(gunit(mine), a, b, seed, offset, prog,
+                                    vals);
+        float4 first, second;
+        float give[4], got[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          // Two values, then the choice: `odd ? vals[e] : vals[4 + e]` is
+          // an lvalue, i.e. a run-time address into vals, i.e. scratch.
+          const float lower = vals[e];
+          const float upper = vals[4 + e];
+          give[e] = from_float<float>(odd ? lower : upper);
+          got[e] = __shfl_xor(give[e], 1);
+        }
+        // Even lane: its unit's lower half, then the odd lane's unit's
+        // lower half. Odd lane: the even lane's unit's upper half, then
+        // its own unit's upper half.
+        first.x = odd ? got[0] : from_float<float>(vals[0]);
+        first.y = odd ? got[1] : from_float<float>(vals[1]);
+        first.z = odd ? got[2] : from_float<float>(vals[2]);
+        first.w = odd ? got[3] : from_float<float>(vals[3]);
+        second.x = odd ? from_float<float>(vals[4]) : got[0];
+        second.y = odd ? from_float<float>(vals[5]) : got[1];
+        second.z = odd ? from_float<float>(vals[6]) : got[2];
+        second.w = odd ? from_float<float>(vals[7]) : got[3];
+        float* p = out +
+                   (static_cast<uint64_t>(chunk) + (lane >> 1)) * kCastUnit +
+                   odd * 4;
+        *reinterpret_cast<float4*>(p) = first;
+        *reinterpret_cast<float4*>(p + 32 * kCastUnit) = second;
+        continue;
+      }
+    }
+    castUnitValues<TSrc, kDist>(gunit(j), a, b, seed, offset, prog, vals);
+    storeCastUnit<TDst>(out + static_cast<uint64_t>(j) * kCastUnit, vals);
+  }
+}
+
+// rng_chain_window_kernel's geometry and index-width rule with the unit in
+// place of the source group. The vector path needs the UNIT whole and
+// aligned: `vec_ok` (the host's check that `out` is 16-byte aligned),
+// g_off % 8 == 0, and a single block or block_len and g_stride both
+// multiples of 8.
+// NB g_off % 8 == 4 with an f32 source: the window starts on a source
+// GROUP boundary (4 elements), so rng_chain_window_kernel<float> would
+// vectorize it — but a unit would then straddle global units (the second
+// group of one and the first of the next) and its 16-byte destination
+// store pairs up differently. It takes the elementwise path here, like
+// every other g_off that is not a unit multiple.
+// A single block whose length is no unit multiple stores its one partial
+// last unit elementwise from one thread; with an f32 source that unit may
+// span a full group and a partial one, so storePartialCastUnit draws the
+// whole unit (both groups) and stores its first elements.
+template <typename TSrc, typename TDst, Dist kDist, typename IdxT>
+__global__ void rng_chain_cast_window_kernel(TDst* __restrict__ out,
+                                             IdxT n_blocks,
+                                             IdxT block_len,
+                                             int64_t g_stride,
+                                             int64_t g_off,
+                                             bool vec_ok,
+                                             float a,
+                                             float b,
+                                             uint64_t seed,
+                                             uint64_t offset,
+                                             TailProgram prog) {
+  const IdxT stride = static_cast<IdxT>(gridDim.x) * blockDim.x;
+  const IdxT tid = blockIdx.x * static_cast<IdxT>(blockDim.x) + threadIdx.x;
+  const bool vec_aligned =
+      vec_ok && (g_off % kCastUnit) == 0 &&
+      (n_blocks == 1 ||
+       ((block_len % kCastUnit) == 0 && (g_stride % kCastUnit) == 0));
+  if (vec_aligned) {
+    const IdxT upb = block_len / kCastUnit;  // full units per window block
+    const IdxT n_units = n_blocks * upb;
+    const uint64_t u0 = static_cast<uint64_t>(g_off) / kCastUnit;
+    const uint64_t us = static_cast<uint64_t>(g_stride) / kCastUnit;
+    castUnitLoop<TSrc, TDst, kDist, IdxT>(
+        out, tid, n_units, stride,
+        [=](IdxT j) -> uint64_t {
+          const IdxT blk = j / upb;
+          const IdxT within = j - blk * upb;
+          return u0 + static_cast<uint64_t>(blk) * us + within;
+        },
+        a, b, seed, offset, prog);
+    // Only a single block can have a partial last unit here.
+    const uint32_t tail_elems =
+        static_cast<uint32_t>(block_len - upb * kCastUnit);
+    if (tail_elems != 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+      storePartialCastUnit<TSrc, TDst, kDist>(
+          out + static_cast<uint64_t>(upb) * kCastUnit, tail_elems, u0 + upb,
+          a, b, seed, offset, prog);
+    }
+    return;
+  }
+  const IdxT n = n_blocks * block_len;
+  for (IdxT i = tid; i < n; i += stride) {
+    const IdxT blk = i / block_len;
+    const IdxT rem = i - blk * block_len;
+    const uint64_t ge = static_cast<uint64_t>(g_off) +
+                        static_cast<uint64_t>(blk) * g_stride + rem;
+    out[i] = castElementValue<TSrc, TDst, kDist>(ge, a, b, seed, offset,
+                                                 prog);
+  }
+}
+
+int castDtypeCode(c10::ScalarType t) {
+  switch (t) {
+    case at::kFloat:
+      return 0;
+    case at::kBFloat16:
+      return 1;
+    case at::kHalf:
+      return 2;
+    default:
+      return -1;
+  }
+}
+
+// Calls f(TSrc{}, TDst{}) for the pair of two DIFFERENT dtype codes.
+template <typename F>
+void dispatchCastPair(int src, int dst, F&& f) {
+  switch (src * 3 + dst) {
+    case 0 * 3 + 1:
+      f(float{}, __hip_bfloat16{});
+      break;
+    case 0 * 3 + 2:
+      f(float{}, __half{});
+      break;
+    case 1 * 3 + 0:
+      f(__hip_bfloat16{}, float{});
+      break;
+    case 1 * 3 + 2:
+      f(__hip_bfloat16{}, __half{});
+      break;
+    case 2 * 3 + 0:
+      f(__half{}, float{});
+      break;
+    case 2 * 3 + 1:
+      f(__half{}, __hip_bfloat16{});
+      break;
+    default:
+      TORCH_CHECK(false, "rng_chain_cast: two different dtypes of "
+                         "float32/bf16/fp16 are required");
+  }
+}
+
+template <Dist kDist>
+void launchRngChainCastWindow(at::Tensor& shard, c10::ScalarType src_dtype,
+                              int64_t n_blocks, int64_t block_len,
+                              int64_t g_stride, int64_t g_off, double p0,
+                              double p1, const TailProgram& prog,
+                              int64_t seed, int64_t offset) {
+  float a = static_cast<float>(p0);
+  float b = kDist == Dist::kUniform ? static_cast<float>(p1 - p0)
+                                    : static_cast<float>(p1);
+  const bool vec_ok =
+      reinterpret_cast<uintptr_t>(shard.data_ptr()) % 16 == 0;
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const int64_t n_work = (shard.numel() + kCastUnit - 1) / kCastUnit;
+  dispatchCastPair(
+      castDtypeCode(src_dtype), castDtypeCode(shard.scalar_type()),
+      [&](auto src_tag, auto dst_tag) {
+        using TSrc = decltype(src_tag);
+        using TDst = decltype(dst_tag);
+        auto launch_idx = [&](auto idx_tag) {
+          using IdxT = decltype(idx_tag);
+          hipLaunchKernelGGL(
+              (rng_chain_cast_window_kernel<TSrc, TDst, kDist, IdxT>),
+              dim3(numBlocks(n_work)), dim3(kBlock), 0, stream.stream(),
+              reinterpret_cast<TDst*>(shard.data_ptr()),
+              static_cast<IdxT>(n_blocks), static_cast<IdxT>(block_len),
+              g_stride, g_off, vec_ok, a, b, static_cast<uint64_t>(seed),
+              static_cast<uint64_t>(offset), prog);
+          C10_HIP_KERNEL_LAUNCH_CHECK();
+        };
+        if (shard.numel() <= std::numeric_limits<int32_t>::max()) {
+          launch_idx(uint32_t{});
+        } else {
+          launch_idx(int64_t{});
+        }
+      });
+}
+
+at::Tensor& tdx_rng_chain_cast_shard_win_(
+    at::Tensor& shard, at::ScalarType src_dtype, int64_t n_blocks,
+    int64_t block_len, int64_t g_stride, int64_t g_off, int64_t dist,
+    double p0, double p1, at::IntArrayRef tail_ops,
+    at::ArrayRef<double> tail_s0, at::ArrayRef<double> tail_s1,
+    int64_t full_numel, int64_t seed, int64_t offset) {
+  TORCH_CHECK(castDtypeCode(src_dtype) >= 0 &&
+                  castDtypeCode(shard.scalar_type()) >= 0 &&
+                  src_dtype != shard.scalar_type(),
+              "rng_chain_cast: two different dtypes of float32/bf16/fp16, "
+              "got ", src_dtype, " -> ", shard.scalar_type());
+  TORCH_CHECK(shard.is_contiguous(),
+              "tdx shard kernels require contiguous tensors");
+  TORCH_CHECK(n_blocks >= 0 && block_len >= 0 && g_stride >= block_len &&
+                  g_off >= 0,
+              "invalid shard window");
+  TORCH_CHECK(shard.numel() == n_blocks * block_len,
+              "shard numel must equal n_blocks * block_len");
+  TORCH_CHECK(full_numel >= g_off + (n_blocks > 0 ? (n_blocks - 1) * g_stride
+                                                  + block_len : 0),
+              "rng_chain: the window does not fit in full_numel");
+  const TailProgram prog =
+      makeTailProgram(tail_ops, tail_s0, tail_s1, full_numel);
+  TORCH_CHECK(0 <= dist && dist <= 2,
+              "rng_chain: dist must be 0 (uniform), 1 (normal) or 2 "
+              "(bernoulli), got ", dist);
+  TORCH_CHECK(dist != 1 || p1 >= 0.0,
+              "normal_ expects std >= 0.0, but found std=", p1);
+  TORCH_CHECK(dist != 2 || (0.0 <= p0 && p0 <= 1.0),
+              "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
+  if (shard.numel() == 0) {
+    return shard;
+  }
+  switch (dist) {
+    case 0:
+      launchRngChainCastWindow<Dist::kUniform>(shard, src_dtype, n_blocks,
+                                               block_len, g_stride, g_off,
+                                               p0, p1, prog, seed, offset);
+      break;
+    case 1:
+      launchRngChainCastWindow<Dist::kNormal>(shard, src_dtype, n_blocks,
+                                              block_len, g_stride, g_off, p0,
+                                              p1, prog, seed, offset);
+      break;
+    default:
+      launchRngChainCastWindow<Dist::kBernoulli>(shard, src_dtype, n_blocks,
+                                                 block_len, g_stride, g_off,
+                                                 p0, 0.0, prog, seed, offset);
+      break;
+  }
+  return shard;
+}
+
+at::Tensor& tdx_rng_chain_cast_(at::Tensor& self, at::ScalarType src_dtype,
+                                int64_t dist, double p0, double p1,
+                                at::IntArrayRef tail_ops,
+                                at::ArrayRef<double> tail_s0,
+                                at::ArrayRef<double> tail_s1, int64_t seed,
+                                int64_t offset) {
+  return tdx_rng_chain_cast_shard_win_(self, src_dtype, 1, self.numel(),
+                                       self.numel(), 0, dist, p0, p1,
+                                       tail_ops, tail_s0, tail_s1,
+                                       self.numel(), seed, offset);
+}
+
+// ---------------------------------------------------------------------------
 // N-d box kernel: materializes full[lo_0:hi_0, ..., lo_{r-1}:hi_{r-1}] of a
 // contiguous virtual full tensor. The box arrives normalized (BoxGeometry
 // in csrc/core/box_geometry.h): equally long contiguous runs nested under
@@ -1692,17 +2086,333 @@ __global__ void batched_init_kernel(const uint8_t* __restrict__ blob,
   }
 }
 
+// fillRangeVec for a tensor whose chain ends in a dtype conversion: drawn
+// and run through the tail at TSrc, stored as TDst, in units of 8 elements
+// (castUnitLoop). begin is kInitEPB-aligned and kInitEPB is a unit
+// multiple, so virtual blocks start on a unit; only the tensor's last
+// vblock can carry a partial unit, stored elementwise by one thread.
+static_assert(kInitEPB % kCastUnit == 0 && (kInitEPB / kCastUnit) % 64 == 0,
+              "virtual blocks must start on a unit, at lane 0 of a wave");
+
+template <typename TSrc, typename TDst, Dist kDist>
+__device__ __forceinline__ void fillRangeCast(TDst* __restrict__ out,
+                                              int64_t begin, int64_t end,
+                                              float a, float b,
+                                              uint64_t seed, uint64_t offset,
+                                              const TailProgram& tail) {
+  const int64_t full_end =
+      begin + ((end - begin) / kCastUnit) * kCastUnit;
+  castUnitLoop<TSrc, TDst, kDist, int64_t>(
+      out, begin / kCastUnit + threadIdx.x, full_end / kCastUnit,
+      static_cast<int64_t>(blockDim.x),
+      [](int64_t j) -> uint64_t { return static_cast<uint64_t>(j); }, a, b,
+      seed, offset, tail);
+  if (threadIdx.x == 0 && full_end < end) {
+    storePartialCastUnit<TSrc, TDst, kDist>(
+        out + full_end, static_cast<uint32_t>(end - full_end),
+        static_cast<uint64_t>(full_end / kCastUnit), a, b, seed, offset,
+        tail);
+  }
+}
+
+template <typename TSrc, typename TDst>
+__device__ __forceinline__ void castDispatchDist(void* ptr, int32_t dist,
+                                                 float a, float b,
+                                                 uint64_t seed,
+                                                 uint64_t offset,
+                                                 int64_t begin, int64_t end,
+                                                 const TailProgram& tail) {
+  TDst* out = static_cast<TDst*>(ptr);
+  switch (dist) {
+    case 0:
+      fillRangeCast<TSrc, TDst, Dist::kUniform>(out, begin, end, a, b, seed,
+                                                offset, tail);
+      break;
+    case 1:
+      fillRangeCast<TSrc, TDst, Dist::kNormal>(out, begin, end, a, b, seed,
+                                               offset, tail);
+      break;
+    default:  // 2; the host admits RNG plans only
+      fillRangeCast<TSrc, TDst, Dist::kBernoulli>(out, begin, end, a, b, seed,
+                                                  offset, tail);
+      break;
+  }
+}
+
+// The batched kernel for tensors with a conversion; batches without one
+// never launch it, and batched_init_kernel is untouched by it. One
+// instantiation: the (source, destination) pair and the distribution are
+// uniform per virtual block, so the dispatch is scalar branches. blob
+// layout: int64 prefix[n], InitTensorMeta[n] (dtype = the destination's),
+// TailProgram[n] (always present, n == 0 for none), int32 src_dtype[n].
+__global__ void batched_init_cast_kernel(const uint8_t* __restrict__ blob,
+                                         int32_t n_tensors,
+                                         int64_t total_vblocks) {
+  const int64_t* prefix = reinterpret_cast<const int64_t*>(blob);
+  const InitTensorMeta* metas = reinterpret_cast<const InitTensorMeta*>(
+      blob + sizeof(int64_t) * n_tensors);
+  const TailProgram* tails = reinterpret_cast<const TailProgram*>(
+      blob + (sizeof(int64_t) + sizeof(InitTensorMeta)) * n_tensors);
+  const int32_t* srcs = reinterpret_cast<const int32_t*>(
+      blob + (sizeof(int64_t) + sizeof(InitTensorMeta) +
+              sizeof(TailProgram)) * n_tensors);
+
+  for (int64_t vb = blockIdx.x; vb < total_vblocks; vb += gridDim.x) {
+    int lo = 0, hi = n_tensors - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (prefix[mid] <= vb) {
+        lo = mid;
+      } else {
+        hi = mid - 1;
+      }
+    }
+    const InitTensorMeta mt = metas[lo];
+    const int64_t begin = (vb - prefix[lo]) * kInitEPB;
+    const int64_t end = begin + kInitEPB < mt.n ? begin + kInitEPB : mt.n;
+    const TailProgram& tail = tails[lo];
+    switch (srcs[lo] * 3 + mt.dtype) {
+      case 0 * 3 + 1:
+        castDispatchDist<float, __hip_bfloat16>(
+            mt.ptr, mt.dist, mt.a, mt.b, mt.seed, mt.offset, begin, end, tail);
+        break;
+      case 0 * 3 + 2:
+        castDispatchDist<float, __half>(
+            mt.ptr, mt.dist, mt.a, mt.b, mt.seed, mt.offset, begin, end, tail);
+        break;
+      case 1 * 3 + 0:
+        castDispatchDist<__hip_bfloat16, float>(
+            mt.ptr, mt.dist, mt.a, mt.b, mt.seed, mt.offset, begin, end, tail);
+        break;
+      case 1 * 3 + 2:
+        castDispatchDist<__hip_bfloat16, __half>(
+            mt.ptr, mt.dist, mt.a, mt.b, mt.seed, mt.offset, begin, end, tail);
+        break;
+      case 2 * 3 + 0:
+        castDispatchDist<__half, float>(
+            mt.ptr, mt.dist, mt.a, mt.b, mt.seed, mt.offset, begin, end, tail);
+        break;
+      default:  // 2 * 3 + 1; the host admits the six pairs only
+        castDispatchDist<__half, __hip_bfloat16>(
+            mt.ptr, mt.dist, mt.a, mt.b, mt.seed, mt.offset, begin, end, tail);
+        break;
+    }
+  }
+}
+
+void batchedInitPlain(std::vector<at::Tensor> tensors,
+                      std::vector<int64_t> dists,
+                      std::vector<double> p0s,
+                      std::vector<double> p1s,
+                      std::vector<int64_t> seeds,
+                      std::vector<int64_t> offsets,
+                      std::vector<std::vector<int64_t>> tail_ops,
+                      std::vector<std::vector<double>> tail_s0,
+                      std::vector<std::vector<double>> tail_s1);
+
+// A batch's tensors with a conversion, checked: every tensor's source
+// dtype code and tail program. Everything that can be refused is refused
+// here, before any launch of the batch — the conversion-free part
+// included.
+struct CastBatch {
+  std::vector<int32_t> srcs;
+  std::vector<TailProgram> tails;
+};
+
+CastBatch checkBatchedCast(
+    const std::vector<at::Tensor>& tensors,
+    const std::vector<int64_t>& dists,
+    const std::vector<double>& p1s,
+    const std::vector<std::vector<int64_t>>& tail_ops,
+    const std::vector<std::vector<double>>& tail_s0,
+    const std::vector<std::vector<double>>& tail_s1,
+    const std::vector<at::ScalarType>& src_dtypes) {
+  CastBatch batch;
+  for (size_t t = 0; t < tensors.size(); ++t) {
+    const at::Tensor& x = tensors[t];
+    TORCH_CHECK(x.is_cuda() && x.is_contiguous(),
+                "batched init: contiguous GPU tensors only");
+    TORCH_CHECK(x.device() == tensors[0].device(),
+                "batched init: one device per batch");
+    TORCH_CHECK(0 <= dists[t] && dists[t] <= 2,
+                "batched init: only RNG plans carry a src_dtype");
+    const int dst = castDtypeCode(x.scalar_type());
+    const int src = castDtypeCode(src_dtypes[t]);
+    TORCH_CHECK(dst >= 0 && src >= 0 && dst != src,
+                "batched init: a conversion is between two different "
+                "dtypes of f32/bf16/f16, got ", src_dtypes[t], " -> ",
+                x.scalar_type());
+    // The allocator's blocks are 512-byte aligned; the vector stores need
+    // 16.
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0,
+                "batched init: 16-byte aligned tensors only");
+    TORCH_CHECK(dists[t] != 1 || p1s[t] >= 0.0,
+                "normal_ expects std >= 0.0, but found std=", p1s[t]);
+    batch.srcs.push_back(src);
+    batch.tails.push_back(
+        tail_ops.empty()
+            ? makeTailProgram(at::IntArrayRef{}, at::ArrayRef<double>{},
+                              at::ArrayRef<double>{}, x.numel())
+            : makeTailProgram(tail_ops[t], tail_s0[t], tail_s1[t],
+                              x.numel()));
+  }
+  return batch;
+}
+
+// The second launch of a batch: its tensors with a conversion.
+void batchedInitCast(const std::vector<at::Tensor>& tensors,
+                     const std::vector<int64_t>& dists,
+                     const std::vector<double>& p0s,
+                     const std::vector<double>& p1s,
+                     const std::vector<int64_t>& seeds,
+                     const std::vector<int64_t>& offsets,
+                     const CastBatch& batch) {
+  static_assert(sizeof(InitTensorMeta) % alignof(TailProgram) == 0 &&
+                    sizeof(int64_t) % alignof(TailProgram) == 0 &&
+                    sizeof(TailProgram) % alignof(int32_t) == 0,
+                "the tables must stay aligned behind one another");
+  const size_t n_tensors = tensors.size();
+  const size_t metas_off = sizeof(int64_t) * n_tensors;
+  const size_t tails_off = metas_off + sizeof(InitTensorMeta) * n_tensors;
+  const size_t srcs_off = tails_off + sizeof(TailProgram) * n_tensors;
+  const size_t blob_bytes = srcs_off + sizeof(int32_t) * n_tensors;
+  at::Tensor host_blob = at::empty(
+      {static_cast<int64_t>(blob_bytes)},
+      at::TensorOptions().dtype(at::kByte).pinned_memory(true));
+  auto* base = static_cast<uint8_t*>(host_blob.data_ptr());
+  auto* prefix = reinterpret_cast<int64_t*>(base);
+  auto* metas = reinterpret_cast<InitTensorMeta*>(base + metas_off);
+  auto* tails = reinterpret_cast<TailProgram*>(base + tails_off);
+  auto* srcs = reinterpret_cast<int32_t*>(base + srcs_off);
+  int64_t total_vblocks = 0;
+  for (size_t t = 0; t < n_tensors; ++t) {
+    const at::Tensor& x = tensors[t];
+    InitTensorMeta& mt = metas[t];
+    mt.ptr = x.data_ptr();
+    mt.n = x.numel();
+    mt.dist = static_cast<int32_t>(dists[t]);
+    mt.dtype = castDtypeCode(x.scalar_type());
+    // Same (a, b) mapping as launchRng.
+    mt.a = static_cast<float>(p0s[t]);
+    mt.b = mt.dist == 0 ? static_cast<float>(p1s[t] - p0s[t])
+                        : static_cast<float>(p1s[t]);
+    mt.seed = static_cast<uint64_t>(seeds[t]);
+    mt.offset = static_cast<uint64_t>(offsets[t]);
+    tails[t] = batch.tails[t];
+    srcs[t] = batch.srcs[t];
+    prefix[t] = total_vblocks;
+    total_vblocks += (mt.n + kInitEPB - 1) / kInitEPB;
+  }
+  if (total_vblocks == 0) {
+    return;
+  }
+  at::Tensor dev_blob =
+      host_blob.to(tensors[0].device(), /*non_blocking=*/true);
+  const int grid =
+      static_cast<int>(std::min<int64_t>(total_vblocks, 16384));
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(batched_init_cast_kernel, dim3(grid), dim3(kBlock), 0,
+                     stream.stream(),
+                     static_cast<const uint8_t*>(dev_blob.const_data_ptr()),
+                     static_cast<int32_t>(n_tensors), total_vblocks);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
 }  // namespace
 
-void batched_init_launch(std::vector<at::Tensor> tensors,
-                         std::vector<int64_t> dists,
-                         std::vector<double> p0s,
-                         std::vector<double> p1s,
-                         std::vector<int64_t> seeds,
-                         std::vector<int64_t> offsets,
-                         std::vector<std::vector<int64_t>> tail_ops,
-                         std::vector<std::vector<double>> tail_s0,
-                         std::vector<std::vector<double>> tail_s1) {
+// `src_dtypes`: nullopt (or all-None) for a batch without conversions,
+// which launches exactly what it always launched. Otherwise one entry per
+// tensor; the tensors with one go into a second launch of their own
+// kernel, the others into the first as before.
+void batched_init_launch(
+    std::vector<at::Tensor> tensors,
+    std::vector<int64_t> dists,
+    std::vector<double> p0s,
+    std::vector<double> p1s,
+    std::vector<int64_t> seeds,
+    std::vector<int64_t> offsets,
+    std::vector<std::vector<int64_t>> tail_ops,
+    std::vector<std::vector<double>> tail_s0,
+    std::vector<std::vector<double>> tail_s1,
+    std::optional<std::vector<std::optional<at::ScalarType>>> src_dtypes) {
+  bool any_cast = false;
+  if (src_dtypes.has_value()) {
+    TORCH_CHECK(src_dtypes->size() == tensors.size(),
+                "batched init: src_dtypes length mismatch");
+    for (const auto& s : *src_dtypes) {
+      any_cast = any_cast || s.has_value();
+    }
+  }
+  if (!any_cast) {
+    batchedInitPlain(std::move(tensors), std::move(dists), std::move(p0s),
+                     std::move(p1s), std::move(seeds), std::move(offsets),
+                     std::move(tail_ops), std::move(tail_s0),
+                     std::move(tail_s1));
+    return;
+  }
+  const size_t n = tensors.size();
+  TORCH_CHECK(dists.size() == n && p0s.size() == n && p1s.size() == n &&
+                  seeds.size() == n && offsets.size() == n,
+              "batched init: list length mismatch");
+  TORCH_CHECK((tail_ops.empty() && tail_s0.empty() && tail_s1.empty()) ||
+                  (tail_ops.size() == n && tail_s0.size() == n &&
+                   tail_s1.size() == n),
+              "batched init: tail list length mismatch");
+  const bool tails_given = !tail_ops.empty();
+  // part[0]: no conversion, part[1]: conversion.
+  struct Part {
+    std::vector<at::Tensor> tensors;
+    std::vector<int64_t> dists, seeds, offsets;
+    std::vector<double> p0s, p1s;
+    std::vector<std::vector<int64_t>> tail_ops;
+    std::vector<std::vector<double>> tail_s0, tail_s1;
+    std::vector<at::ScalarType> srcs;
+  } part[2];
+  for (size_t t = 0; t < n; ++t) {
+    const auto& src = (*src_dtypes)[t];
+    Part& p = part[src.has_value() ? 1 : 0];
+    p.tensors.push_back(tensors[t]);
+    p.dists.push_back(dists[t]);
+    p.p0s.push_back(p0s[t]);
+    p.p1s.push_back(p1s[t]);
+    p.seeds.push_back(seeds[t]);
+    p.offsets.push_back(offsets[t]);
+    if (tails_given) {
+      p.tail_ops.push_back(tail_ops[t]);
+      p.tail_s0.push_back(tail_s0[t]);
+      p.tail_s1.push_back(tail_s1[t]);
+    }
+    if (src.has_value()) {
+      p.srcs.push_back(*src);
+    }
+  }
+  // The conversion part is checked before the plain part launches, so a
+  // refused batch has filled nothing.
+  const CastBatch cast_batch = checkBatchedCast(
+      part[1].tensors, part[1].dists, part[1].p1s, part[1].tail_ops,
+      part[1].tail_s0, part[1].tail_s1, part[1].srcs);
+  if (!part[0].tensors.empty()) {
+    batchedInitPlain(std::move(part[0].tensors), std::move(part[0].dists),
+                     std::move(part[0].p0s), std::move(part[0].p1s),
+                     std::move(part[0].seeds), std::move(part[0].offsets),
+                     std::move(part[0].tail_ops), std::move(part[0].tail_s0),
+                     std::move(part[0].tail_s1));
+  }
+  batchedInitCast(part[1].tensors, part[1].dists, part[1].p0s, part[1].p1s,
+                  part[1].seeds, part[1].offsets, cast_batch);
+}
+
+namespace {
+
+void batchedInitPlain(std::vector<at::Tensor> tensors,
+                      std::vector<int64_t> dists,
+                      std::vector<double> p0s,
+                      std::vector<double> p1s,
+                      std::vector<int64_t> seeds,
+                      std::vector<int64_t> offsets,
+                      std::vector<std::vector<int64_t>> tail_ops,
+                      std::vector<std::vector<double>> tail_s0,
+                      std::vector<std::vector<double>> tail_s1) {
   const size_t n_tensors = tensors.size();
   TORCH_CHECK(n_tensors > 0 && dists.size() == n_tensors &&
                   p0s.size() == n_tensors && p1s.size() == n_tensors &&
@@ -1795,8 +2505,6 @@ void batched_init_launch(std::vector<at::Tensor> tensors,
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
-namespace {
-
 // Schemas are defined by the core extension (csrc/core/tdx_ops.cc); this
 // extension contributes the CUDA implementations.
 TORCH_LIBRARY_IMPL(tdx, CUDA, m) {
@@ -1815,6 +2523,8 @@ TORCH_LIBRARY_IMPL(tdx, CUDA, m) {
   m.impl("rng_chain_", tdx_rng_chain_);
   m.impl("rng_chain_shard_win_", tdx_rng_chain_shard_win_);
   m.impl("rng_box_", tdx_rng_box_);
+  m.impl("rng_chain_cast_", tdx_rng_chain_cast_);
+  m.impl("rng_chain_cast_shard_win_", tdx_rng_chain_cast_shard_win_);
 }
 
 }  // namespace

@@ -28,7 +28,9 @@ void batched_init_launch(std::vector<at::Tensor> tensors,
                          std::vector<int64_t> offsets,
                          std::vector<std::vector<int64_t>> tail_ops,
                          std::vector<std::vector<double>> tail_s0,
-                         std::vector<std::vector<double>> tail_s1);
+                         std::vector<std::vector<double>> tail_s1,
+                         std::optional<std::vector<std::optional<at::ScalarType>>>
+                             src_dtypes);
 
 void anyprecision_adamw_batched_step(
     std::vector<at::Tensor> params,
@@ -55,6 +57,7 @@ PYBIND11_MODULE(_K, m) {
   m.def("has_batched_init", [] { return true; });
   m.def("has_fused_chains", [] { return true; });
   m.def("has_box_kernel", [] { return true; });
+  m.def("has_cast_chains", [] { return true; });
 
   m.def("batched_init_", &tdx::batched_init_launch,
         pybind11::arg("tensors"), pybind11::arg("dists"),
@@ -63,12 +66,17 @@ PYBIND11_MODULE(_K, m) {
         pybind11::arg("tail_ops") = std::vector<std::vector<int64_t>>{},
         pybind11::arg("tail_s0") = std::vector<std::vector<double>>{},
         pybind11::arg("tail_s1") = std::vector<std::vector<double>>{},
+        pybind11::arg("src_dtypes") = pybind11::none(),
         "One launch filling every listed tensor with its reduced init "
         "plan (dist: 0 uniform, 1 normal, 2 bernoulli, 3 fill, 4 zero); "
         "bitwise-identical to the per-tensor tdx kernels. The optional "
         "tail lists give each tensor's fused pointwise tail (opcodes and "
         "scalars as in tdx::rng_chain_; empty for none), applied in "
-        "registers before the store.");
+        "registers before the store. The optional src_dtypes list gives, "
+        "per tensor, the dtype an RNG plan was recorded at when a "
+        "conversion to the tensor's dtype follows it (None for none): "
+        "those tensors fill in a second launch that draws at src_dtype "
+        "and stores the tensor's dtype (as tdx::rng_chain_cast_).");
 
   m.def("anyprecision_adamw_batched_",
         &tdx::anyprecision_adamw_batched_step, pybind11::arg("params"),

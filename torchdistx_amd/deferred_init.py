@@ -181,7 +181,12 @@ def materialize_module_batched(
     richer tapes (views, cross-tensor dependencies, tails outside the
     fusable set such as ``div_`` or ``add_(alpha != 1)``, any tail while
     ``_C.set_fused_init_chains(False)`` is in effect) fall back to
-    ordinary replay. GPU-only; CPU targets use :func:`materialize_module`.
+    ordinary replay. A chain that ends in one dtype conversion between
+    float32/bf16/fp16 — ``Model(cfg).to(torch.bfloat16)`` inside the
+    builder, ``Parameter(empty(..).normal_().to(bf16))`` — is plannable
+    too: its tensors fill in a second launch that draws at the recorded
+    dtype and stores the final one, without a full-precision copy.
+    GPU-only; CPU targets use :func:`materialize_module`.
 
     Launch count for a Llama-3-70B replica drops from ~560 to ~3.
 
@@ -260,8 +265,14 @@ def _batched_fill(entries, device=None) -> list:
         hasattr(_kernels._K, "has_fused_chains")
         and _kernels._K.has_fused_chains()
     )
+    # Chains that end in a dtype conversion (Module.to(dtype) inside the
+    # builder) need the kernels that draw at one dtype and store another.
+    cast = (
+        hasattr(_kernels._K, "has_cast_chains")
+        and _kernels._K.has_cast_chains()
+    )
     batch = {"t": [], "dist": [], "p0": [], "p1": [], "seed": [],
-             "offset": [], "tail": [], "entry": []}
+             "offset": [], "tail": [], "src": [], "entry": []}
     fallback = []
     seen = {}  # id(fake) -> out: tied params must share ONE allocation
     for entry in entries:
@@ -274,8 +285,10 @@ def _batched_fill(entries, device=None) -> list:
         else:
             plan = _C.tensor_init_plan(tensor)
         tail = plan.get("tail", []) if plan is not None else []
+        src_dtype = plan.get("src_dtype") if plan is not None else None
         if (
             plan is None
+            or (src_dtype is not None and not cast)
             or plan["dtype"] not in (
                 torch.float32, torch.bfloat16, torch.float16
             )
@@ -307,10 +320,22 @@ def _batched_fill(entries, device=None) -> list:
             batch["seed"].append(plan["seed"])
             batch["offset"].append(plan["offset"])
             batch["tail"].append(tail)
+            batch["src"].append(src_dtype)
         # kind == "factory": allocate-only, matching aten::empty replay.
         batch["entry"].append((entry, out))
 
-    if batch["t"] and any(batch["tail"]):
+    if batch["t"] and any(d is not None for d in batch["src"]):
+        # Tensors with a conversion fill in a second launch of their own
+        # kernel; the others launch as in the branches below.
+        _kernels._K.batched_init_(
+            batch["t"], batch["dist"], batch["p0"], batch["p1"],
+            batch["seed"], batch["offset"],
+            [[_TAIL_CODE[name] for name, _, _ in t] for t in batch["tail"]],
+            [[s0 for _, s0, _ in t] for t in batch["tail"]],
+            [[s1 for _, _, s1 in t] for t in batch["tail"]],
+            batch["src"],
+        )
+    elif batch["t"] and any(batch["tail"]):
         _kernels._K.batched_init_(
             batch["t"], batch["dist"], batch["p0"], batch["p1"],
             batch["seed"], batch["offset"],
