@@ -11,6 +11,7 @@ def has_batched_init() -> bool: ...
 def has_fused_chains() -> bool: ...
 def has_box_kernel() -> bool: ...
 def has_cast_chains() -> bool: ...
+def has_patch_kernel() -> bool: ...
 def anyprecision_adamw_(
     param: torch.Tensor,
     grad: torch.Tensor,

@@ -202,6 +202,75 @@ inline const char* checkBoxArgs(const int64_t* extents, size_t n_extents,
   return nullptr;
 }
 
+// Rows [first, last) of a box.
+struct RowRange {
+  int64_t first = 0;
+  int64_t last = 0;
+
+  TDX_HD int64_t count() const { return last - first; }
+};
+
+// The rows of `box` that hold at least one element of the full-tensor
+// range [lo, hi). rowStart is strictly increasing in the row index (every
+// stride is at least what the level inside it spans), so these rows are
+// one contiguous range, found by two binary searches: the first row that
+// ends after lo, and the first row that starts at or after hi. Empty boxes
+// and ranges give {0, 0}. Used by tdx::patch_box_, which walks only these
+// rows.
+TDX_HD RowRange rowsMeeting(const BoxGeometry& box, int64_t lo,
+                                   int64_t hi) {
+  RowRange out;
+  const int64_t rows = box.rows();
+  if (box.run_len <= 0 || rows <= 0 || lo >= hi) {
+    return out;
+  }
+  int64_t a = 0;
+  int64_t b = rows;
+  while (a < b) {  // first row with rowStart + run_len > lo
+    const int64_t mid = a + (b - a) / 2;
+    if (box.rowStart(mid) + box.run_len > lo) {
+      b = mid;
+    } else {
+      a = mid + 1;
+    }
+  }
+  const int64_t first = a;
+  b = rows;
+  while (a < b) {  // first row with rowStart >= hi
+    const int64_t mid = a + (b - a) / 2;
+    if (box.rowStart(mid) >= hi) {
+      b = mid;
+    } else {
+      a = mid + 1;
+    }
+  }
+  if (a > first) {
+    out.first = first;
+    out.last = a;
+  }
+  return out;
+}
+
+// Validates the patch arguments of tdx::patch_box_ that checkBoxArgs does
+// not cover. Returns nullptr when they are sound.
+inline const char* checkPatchArgs(int64_t patch_lo, int64_t patch_len,
+                                  int64_t full_numel, int64_t dist,
+                                  bool has_seed, bool has_offset) {
+  int64_t end = 0;
+  if (patch_lo < 0 || patch_len < 0 ||
+      __builtin_add_overflow(patch_lo, patch_len, &end) || end > full_numel) {
+    return "the patch does not fit in full_numel";
+  }
+  if (dist < 0 || dist > 4) {
+    return "dist must be 0 (uniform), 1 (normal), 2 (bernoulli), 3 (fill) "
+           "or 4 (zero)";
+  }
+  if (dist <= 2 && !(has_seed && has_offset)) {
+    return "an RNG patch needs a seed and an offset";
+  }
+  return nullptr;
+}
+
 // Unsigned division by a fixed 32-bit divisor as a multiply-high, an add
 // and a shift (Granlund & Montgomery, "Division by invariant integers
 // using multiplication", PLDI'94): with s = ceil(log2 d) and

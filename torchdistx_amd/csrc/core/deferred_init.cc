@@ -301,6 +301,11 @@ struct OpNode {
     c10::ScalarType dtype = c10::ScalarType::Undefined;
     c10::Device device{c10::DeviceType::CPU};
     bool contiguous = false;
+    // Where the output sits in its storage, in elements: what locates a
+    // view (and an in-place op's target) inside the tensor it was taken
+    // from.
+    int64_t storage_offset = 0;
+    int64_t numel = 0;
   };
   std::vector<OutputMeta> output_metas;
   // tdx::set_data only: the producer `self` had BEFORE the assignment.
@@ -441,7 +446,8 @@ void recordOp(std::string name,
     node->output_storages.push_back(out_storage);
     node->output_metas.push_back(OpNode::OutputMeta{
         fake->meta_tensor().scalar_type(), fake->fake_device(),
-        fake->meta_tensor().is_contiguous()});
+        fake->meta_tensor().is_contiguous(),
+        fake->meta_tensor().storage_offset(), fake->meta_tensor().numel()});
 
     auto rec = getRecord(fake);
     if (rec == nullptr) {
@@ -1205,6 +1211,23 @@ struct ChainStep {
   // Set for a kPointwise step the RNG kernels can apply in registers
   // (fusableTailOp below).
   std::optional<TailOp> tail_op;
+  // In-place value and pointwise steps: the extent of the tensor they ran
+  // on, as recorded (OpNode::OutputMeta). buildChainSteps compares it with
+  // the lineage tensor's own extent.
+  bool in_place = false;
+  bool target_contiguous = false;
+  int64_t target_offset = 0;
+  int64_t target_numel = 0;
+  // kCast / copying kPass: the extent of the SOURCE tensor in in_storage.
+  int64_t in_offset = 0;
+  int64_t in_numel = 0;
+  // Set by buildChainSteps for a value step on a contiguous proper
+  // sub-range of the tensor: it writes flat elements
+  // [patch_lo, patch_lo + patch_len) and leaves the rest alone.
+  bool patch = false;
+  int64_t patch_lo = 0;
+  int64_t patch_len = 0;
+  std::string name;  // the recorded op, for error messages
 };
 
 // A recorded scalar operand of a fusable tail step. Only what ATen turns
@@ -1370,6 +1393,24 @@ bool isAliasPassOpName(const std::string& name) {
          name == "aten::alias";
 }
 
+// View ops that keep their output inside the input's storage. They are
+// pass steps: what matters is the extent of the tensor a later in-place op
+// ran on, which that op's own record holds.
+bool isViewPassOpName(const std::string& name) {
+  static const char* kNames[] = {
+      "aten::select",    "aten::slice",   "aten::narrow",
+      "aten::view",      "aten::_unsafe_view", "aten::reshape",
+      "aten::flatten",   "aten::unflatten",    "aten::squeeze",
+      "aten::unsqueeze",
+  };
+  for (const char* n : kNames) {
+    if (name == n) {
+      return true;
+    }
+  }
+  return false;
+}
+
 bool isFloat3(c10::ScalarType t) {
   return t == at::kFloat || t == at::kBFloat16 || t == at::kHalf;
 }
@@ -1443,6 +1484,8 @@ void classifyToNode(const OpNode& node, ChainStep& step) {
   }
   step.out_of_place = true;
   step.in_storage = in_storage;
+  step.in_offset = in.storage_offset;
+  step.in_numel = in.numel;
   if (in.dtype == out.dtype) {
     step.kind = ChainStep::Kind::kPass;  // copy=True
     return;
@@ -1473,9 +1516,23 @@ ChainStep classifyChainNode(const OpNode& node) {
     TORCH_CHECK(false, "slice materialization: unexpected argument type `",
                 v.tagKind(), "` in `", op.name, "`");
   };
+  step.name = op.name;
   if (!node.output_metas.empty()) {
     step.dtype = node.output_metas[0].dtype;
+    step.target_offset = node.output_metas[0].storage_offset;
+    step.target_numel = node.output_metas[0].numel;
   }
+  auto markInPlace = [&] {
+    TORCH_CHECK(!node.output_metas.empty() && node.output_storages[0],
+                "slice materialization: `", op.name,
+                "` was recorded without its target; materialize the tensor "
+                "fully instead.");
+    const OpNode::OutputMeta& out = node.output_metas[0];
+    step.in_place = true;
+    step.target_contiguous = out.contiguous;
+    step.target_offset = out.storage_offset;
+    step.target_numel = out.numel;
+  };
   if (isToOpName(op.name)) {
     classifyToNode(node, step);
   } else if (op.name == "tdx::set_data") {
@@ -1513,12 +1570,23 @@ ChainStep classifyChainNode(const OpNode& node) {
       step.p1 = scalarArg(2);
     }
     step.philox = op.philox;
+    markInPlace();
   } else if (op.name == "aten::fill_") {
     step.kind = ChainStep::Kind::kFill;
     step.p0 = scalarArg(1);
+    markInPlace();
   } else if (op.name == "aten::zero_") {
     step.kind = ChainStep::Kind::kZero;
+    markInPlace();
   } else if (isAliasPassOpName(op.name)) {
+    step.kind = ChainStep::Kind::kPass;
+  } else if (isViewPassOpName(op.name) && !node.input_slots.empty() &&
+             node.input_slots[0].desc.has_value() &&
+             !node.output_storages.empty() &&
+             storagesAlias(
+                 node.output_storages[0],
+                 node.input_slots[0].desc->node->output_storages.at(
+                     node.input_slots[0].desc->index))) {
     step.kind = ChainStep::Kind::kPass;
   } else if (isPointwiseScalarOpName(op.name) &&
              std::all_of(op.args.begin() + 1, op.args.end(),
@@ -1527,6 +1595,7 @@ ChainStep classifyChainNode(const OpNode& node) {
     step.pointwise_args.assign(op.args.begin() + 1, op.args.end());
     step.pointwise_run = op.run;
     step.tail_op = fusableTailOp(op.name, step.pointwise_args);
+    markInPlace();
   } else {
     TORCH_CHECK(false, "slice materialization: `", op.name,
                 "` is not a whole-tensor init op; materialize the tensor "
@@ -1584,8 +1653,68 @@ void applyBoxStep(const ChainStep& rng, const std::vector<TailOp>& tail,
                static_cast<int64_t>(rng.philox->second));
 }
 
+// dist code of a value step in the _DIST_CODE numbering of the batched
+// planner and tdx::patch_box_: 0 uniform, 1 normal, 2 bernoulli, 3 fill,
+// 4 zero.
+int64_t valueDistCode(ChainStep::Kind kind) {
+  switch (kind) {
+    case ChainStep::Kind::kUniform:
+      return 0;
+    case ChainStep::Kind::kNormal:
+      return 1;
+    case ChainStep::Kind::kBernoulli:
+      return 2;
+    case ChainStep::Kind::kFill:
+      return 3;
+    default:
+      return 4;
+  }
+}
+
+// One tdx::patch_box_ call: the value step (dist, p0, p1, philox) on flat
+// elements [lo, lo + len) of the full tensor, applied to what the window
+// (or box) `w` holds of them, at the shard's dtype.
+void applyPatchOp(at::Tensor& shard, const ShardWindow& w, int64_t full_numel,
+                  int64_t lo, int64_t len, int64_t dist, double p0, double p1,
+                  const std::optional<std::pair<uint64_t, uint64_t>>& philox) {
+  static const auto patch_box =
+      c10::Dispatcher::singleton()
+          .findSchemaOrThrow("tdx::patch_box_", "")
+          .typed<at::Tensor&(at::Tensor&, at::IntArrayRef, at::IntArrayRef,
+                             int64_t, int64_t, int64_t, int64_t, int64_t,
+                             int64_t, double, double, std::optional<int64_t>,
+                             std::optional<int64_t>)>();
+  TORCH_CHECK(dist > 2 || philox.has_value(),
+              "slice materialization: this RNG op carries no pinned "
+              "Philox state (was it recorded by an older build?)");
+  std::optional<int64_t> seed;
+  std::optional<int64_t> offset;
+  if (philox.has_value()) {
+    seed = static_cast<int64_t>(philox->first);
+    offset = static_cast<int64_t>(philox->second);
+  }
+  if (w.box.has_value()) {
+    const BoxGeometry& box = *w.box;
+    patch_box.call(shard, at::IntArrayRef(box.extent, box.levels),
+                   at::IntArrayRef(box.g_stride, box.levels), box.run_len,
+                   box.g_off, full_numel, lo, len, dist, p0, p1, seed, offset);
+    return;
+  }
+  // A flat range or single-dim window is the one-level box it is.
+  const int64_t extent = w.n_blocks;
+  const int64_t stride = std::max(w.g_stride, w.block_len);
+  patch_box.call(shard, at::IntArrayRef(&extent, 1),
+                 at::IntArrayRef(&stride, 1), w.block_len, w.g_off,
+                 full_numel, lo, len, dist, p0, p1, seed, offset);
+}
+
 void applyShardStep(const ChainStep& step, at::Tensor& shard,
                     const ShardWindow& w, int64_t full_numel) {
+  if (step.patch) {
+    applyPatchOp(shard, w, full_numel, step.patch_lo, step.patch_len,
+                 valueDistCode(step.kind), step.p0, step.p1, step.philox);
+    return;
+  }
   switch (step.kind) {
     case ChainStep::Kind::kFactory:
     case ChainStep::Kind::kPass:
@@ -1786,6 +1915,15 @@ bool tailOpAdmitted(const TailOp& op, c10::ScalarType dtype, int64_t numel) {
   return !inexact || fusedInitChainsExplicit();
 }
 
+// The steps that set every element they run on, whatever it held before.
+bool isValueStep(const ChainStep& step) {
+  return step.kind == ChainStep::Kind::kUniform ||
+         step.kind == ChainStep::Kind::kNormal ||
+         step.kind == ChainStep::Kind::kBernoulli ||
+         step.kind == ChainStep::Kind::kFill ||
+         step.kind == ChainStep::Kind::kZero;
+}
+
 bool isRngStep(const ChainStep& step) {
   return step.kind == ChainStep::Kind::kUniform ||
          step.kind == ChainStep::Kind::kNormal ||
@@ -1843,8 +1981,21 @@ bool setDataFollowsLineage(const std::vector<std::shared_ptr<OpNode>>& nodes,
 // conversion into its source's storage, and drops conversions that
 // produced some OTHER tensor (the replay set pulls in `h = p.half()` when
 // p is overwritten afterwards; h is no part of p).
+//
+// In-place steps are placed by the extent of the tensor they ran on,
+// relative to the lineage tensor's own [offset, offset + numel) in the
+// storage the step acts on:
+//  * the whole tensor, contiguously: a whole-tensor step, as recorded on
+//    the tensor itself (`w.view(-1).normal_()` is `w.normal_()`);
+//  * a contiguous proper sub-range, for a value step: a PATCH
+//    (`w[i].zero_()`, `w[:k].normal_()`), honoured in tape order;
+//  * nothing of the tensor (a sibling view of a shared buffer): dropped;
+//  * anything else (a strided view, a pointwise op on a sub-view, a
+//    range that only partly covers the tensor) throws.
+// A whole-tensor value step makes every earlier patch dead (it becomes a
+// pass step); a whole-tensor pointwise step behind a live patch throws.
 std::vector<ChainStep> buildChainSteps(const TensorRecord& rec,
-                                       const c10::Storage& final_storage) {
+                                       const at::Tensor& final_meta) {
   auto nodes = buildCallStack(rec);
   std::vector<ChainStep> all;
   all.reserve(nodes.size());
@@ -1854,22 +2005,54 @@ std::vector<ChainStep> buildChainSteps(const TensorRecord& rec,
   std::vector<char> keep(all.size(), 1);
   std::vector<char> in_lineage(all.size(), 1);
   bool crosses = false;
-  c10::Storage cur = final_storage;
+  c10::Storage cur = final_meta.storage();
+  int64_t cur_off = final_meta.storage_offset();
+  int64_t cur_numel = final_meta.numel();
   for (size_t i = all.size(); i-- > 0;) {
     const bool in = outputsAlias(*nodes[i], cur);
     in_lineage[i] = in;
-    if (all[i].out_of_place) {
+    ChainStep& step = all[i];
+    if (step.out_of_place) {
       if (!in) {
         keep[i] = 0;
         continue;
       }
       crosses = true;
-      cur = all[i].in_storage;
-    } else if (all[i].is_set_data) {
+      cur = step.in_storage;
+      cur_off = step.in_offset;
+      cur_numel = step.in_numel;
+    } else if (step.is_set_data) {
       TORCH_CHECK(in && setDataFollowsLineage(nodes, all, i),
                   "slice materialization: `tdx::set_data` assigns a tensor "
                   "of another lineage, which is not a whole-tensor init op; "
                   "materialize the tensor fully instead.");
+    } else if (step.in_place && in) {
+      TORCH_CHECK(step.target_contiguous,
+                  "slice materialization: `", step.name,
+                  "` ran on a non-contiguous view, which is not a "
+                  "whole-tensor init op; materialize the tensor fully "
+                  "instead.");
+      const int64_t lo = step.target_offset - cur_off;
+      const int64_t hi = lo + step.target_numel;
+      if (lo == 0 && hi == cur_numel) {
+        continue;  // the whole tensor
+      }
+      if (hi <= 0 || lo >= cur_numel || step.target_numel == 0) {
+        keep[i] = 0;  // touches nothing of this tensor
+        continue;
+      }
+      TORCH_CHECK(0 <= lo && hi <= cur_numel,
+                  "slice materialization: `", step.name,
+                  "` ran on a tensor that only partly overlaps this one, "
+                  "which is not a whole-tensor init op; materialize the "
+                  "tensor fully instead.");
+      TORCH_CHECK(step.kind != ChainStep::Kind::kPointwise,
+                  "slice materialization: `", step.name,
+                  "` on a sub-view is not a whole-tensor init op; "
+                  "materialize the tensor fully instead.");
+      step.patch = true;
+      step.patch_lo = lo;
+      step.patch_len = hi - lo;
     }
   }
   std::vector<ChainStep> steps;
@@ -1883,6 +2066,33 @@ std::vector<ChainStep> buildChainSteps(const TensorRecord& rec,
                 "with ops on another tensor; materialize the tensor fully "
                 "instead.");
     steps.push_back(std::move(all[i]));
+  }
+  // Liveness: patches before the last whole-tensor value step are dead.
+  size_t last_whole = 0;
+  bool have_whole = false;
+  for (size_t i = 0; i < steps.size(); ++i) {
+    if (isValueStep(steps[i]) && !steps[i].patch) {
+      last_whole = i;
+      have_whole = true;
+    }
+  }
+  bool live_patch = false;
+  for (size_t i = 0; i < steps.size(); ++i) {
+    ChainStep& step = steps[i];
+    if (step.patch && have_whole && i < last_whole) {
+      ChainStep pass;
+      pass.kind = ChainStep::Kind::kPass;
+      pass.dtype = step.dtype;
+      pass.name = step.name;
+      step = std::move(pass);
+    } else if (step.patch) {
+      live_patch = true;
+    } else if (step.kind == ChainStep::Kind::kPointwise) {
+      TORCH_CHECK(!live_patch, "slice materialization: `", step.name,
+                  "` follows a partial-tensor write, which is not a "
+                  "whole-tensor init chain; materialize the tensor fully "
+                  "instead.");
+    }
   }
   return steps;
 }
@@ -1965,8 +2175,13 @@ std::optional<double> roundScalarThrough(double v, c10::ScalarType dtype) {
 }
 
 // Shared body of tensorInitPlan (allow_tail == false) and tensorChainPlan.
+// With `patches` set, live patches are collected there in application
+// order (tensorPatchPlan); without it a chain with a live patch has no
+// plan.
 std::optional<ChainPlan> chainPlanImpl(const at::Tensor& tensor,
-                                       bool allow_tail) {
+                                       bool allow_tail,
+                                       std::vector<PatchStep>* patches =
+                                           nullptr) {
   auto* fake = asFake(tensor);
   if (fake == nullptr) {
     return std::nullopt;
@@ -1983,13 +2198,52 @@ std::optional<ChainPlan> chainPlanImpl(const at::Tensor& tensor,
   ChainPlan plan;
   try {
     const std::vector<ChainStep> steps =
-        buildChainSteps(*rec, meta.storage());
+        buildChainSteps(*rec, meta);
+    // The plan stands for a tensor with a storage of its own: a view of a
+    // larger buffer keeps its aliasing only through ordinary replay.
+    if (!steps.empty() && !steps.front().in_place &&
+        (steps.front().kind == ChainStep::Kind::kFactory ||
+         steps.front().kind == ChainStep::Kind::kZero ||
+         steps.front().kind == ChainStep::Kind::kFill) &&
+        (meta.storage_offset() != 0 ||
+         steps.front().target_numel != meta.numel())) {
+      return std::nullopt;
+    }
     bool have_value = false;
+    std::vector<char> patch_before_cast;
     bool tail_unfusable = false;  // a live pointwise step we cannot fuse
     // At most one conversion, and nothing that changes values behind it:
     // the kernels generate at one dtype and store at another, once.
     std::optional<c10::ScalarType> cast_src;
     for (const ChainStep& step : steps) {
+      if (step.patch) {
+        // Live by construction (buildChainSteps), and behind the tail.
+        if (patches == nullptr ||
+            (isRngStep(step) && !step.philox.has_value())) {
+          return std::nullopt;
+        }
+        PatchStep ps;
+        ps.lo = step.patch_lo;
+        ps.len = step.patch_len;
+        ps.kind = step.kind == ChainStep::Kind::kUniform
+                      ? InitPlan::Kind::kUniform
+                      : (step.kind == ChainStep::Kind::kNormal
+                             ? InitPlan::Kind::kNormal
+                             : (step.kind == ChainStep::Kind::kBernoulli
+                                    ? InitPlan::Kind::kBernoulli
+                                    : (step.kind == ChainStep::Kind::kFill
+                                           ? InitPlan::Kind::kFill
+                                           : InitPlan::Kind::kZero)));
+        ps.p0 = step.p0;
+        ps.p1 = step.p1;
+        if (step.philox.has_value()) {
+          ps.seed = step.philox->first;
+          ps.offset = step.philox->second;
+        }
+        patches->push_back(ps);
+        patch_before_cast.push_back(!cast_src.has_value());
+        continue;
+      }
       if (cast_src.has_value() && step.kind != ChainStep::Kind::kPass &&
           step.kind != ChainStep::Kind::kFactory) {
         return std::nullopt;
@@ -2059,6 +2313,24 @@ std::optional<ChainPlan> chainPlanImpl(const at::Tensor& tensor,
         return std::nullopt;
       }
     }
+    if (cast_src.has_value() && patches != nullptr) {
+      for (size_t i = 0; i < patches->size(); ++i) {
+        PatchStep& ps = (*patches)[i];
+        // An RNG patch draws at the dtype it was recorded at; only the
+        // segment replay serves that next to a conversion.
+        if (ps.kind != InitPlan::Kind::kFill &&
+            ps.kind != InitPlan::Kind::kZero) {
+          return std::nullopt;
+        }
+        if (patch_before_cast[i]) {
+          auto rounded = roundScalarThrough(ps.p0, *cast_src);
+          if (!rounded.has_value()) {
+            return std::nullopt;
+          }
+          ps.p0 = *rounded;
+        }
+      }
+    }
     if (cast_src.has_value()) {
       switch (plan.kind) {
         case InitPlan::Kind::kUniform:
@@ -2104,7 +2376,7 @@ at::Tensor replayChainOnShard(FakeTensorImpl* fake,
   const at::Tensor& meta = fake->meta_tensor();
   std::lock_guard<std::recursive_mutex> lock{tape_mutex};
   auto rec = getRecord(fake);
-  const std::vector<ChainStep> steps = buildChainSteps(*rec, meta.storage());
+  const std::vector<ChainStep> steps = buildChainSteps(*rec, meta);
   TORCH_CHECK(!steps.empty() &&
                   (steps.front().kind == ChainStep::Kind::kFactory ||
                    steps.front().kind == ChainStep::Kind::kZero ||
@@ -2120,30 +2392,70 @@ at::Tensor replayChainOnShard(FakeTensorImpl* fake,
     return tail;
   };
 
+  // Live patches sit behind the tail (buildChainSteps); with them read as
+  // pass steps the fused runs below are found as for a patch-free chain.
+  std::vector<ChainStep> plain = steps;
+  bool rng_patch = false;
+  for (ChainStep& step : plain) {
+    if (step.patch) {
+      rng_patch = rng_patch || isRngStep(step);
+      step.kind = ChainStep::Kind::kPass;
+      step.patch = false;
+    }
+  }
+
   // [RNG step, tail..., one cast] at the end of the chain is one launch
   // that draws at the source dtype and stores the final one; everything
   // before the RNG step is overwritten by it. A box of two or more levels
   // has no cast kernel: it takes the segments below (the box op at the
   // source dtype into a block-sized temporary, then the conversion).
-  if (!w.box.has_value()) {
-    const auto run = fusedRunStart(steps, 0, steps.size(), meta.numel(),
+  // Constant patches go on afterwards at the final dtype, a patch from
+  // before the conversion with its value rounded through the source dtype
+  // first; an RNG patch draws at the dtype it was recorded at, so a chain
+  // with one takes the segments.
+  if (!w.box.has_value() && !rng_patch) {
+    const auto run = fusedRunStart(plain, 0, plain.size(), meta.numel(),
                                    /*allow_cast=*/true);
     if (run.has_value() && run->cast.has_value()) {
-      at::Tensor shard =
-          at::empty(shard_sizes, options.dtype(steps[*run->cast].cast_to));
-      applyFusedCastShardStep(steps[run->rng], tailOf(*run),
-                              steps[*run->cast].dtype, shard, w,
-                              meta.numel());
-      return shard;
+      std::vector<double> values;
+      bool representable = true;
+      for (size_t i = run->tail_end; i < steps.size(); ++i) {
+        if (!steps[i].patch) {
+          continue;
+        }
+        std::optional<double> v = steps[i].p0;
+        if (i < *run->cast) {
+          v = roundScalarThrough(steps[i].p0, steps[*run->cast].dtype);
+        }
+        representable = representable && v.has_value();
+        values.push_back(v.value_or(0.0));
+      }
+      if (representable) {
+        at::Tensor shard =
+            at::empty(shard_sizes, options.dtype(steps[*run->cast].cast_to));
+        applyFusedCastShardStep(steps[run->rng], tailOf(*run),
+                                steps[*run->cast].dtype, shard, w,
+                                meta.numel());
+        size_t n = 0;
+        for (size_t i = run->tail_end; i < steps.size(); ++i) {
+          if (steps[i].patch) {
+            applyPatchOp(shard, w, meta.numel(), steps[i].patch_lo,
+                         steps[i].patch_len, valueDistCode(steps[i].kind),
+                         values[n++], 0.0, std::nullopt);
+          }
+        }
+        return shard;
+      }
     }
   }
 
   // Otherwise the chain runs in segments of one dtype each, split at its
   // conversions. The shard starts at the chain's FIRST dtype; within a
-  // segment a trailing [RNG step, fusable tail...] run is one fused
-  // launch and any other arrangement applies step by step; a conversion
-  // replaces the shard by its converted copy. Only shard-sized tensors
-  // exist at any point.
+  // segment a [RNG step, fusable tail...] run followed only by pass steps
+  // and patches is one fused launch and any other arrangement applies step
+  // by step; a patch is one tdx::patch_box_ call at the segment's dtype; a
+  // conversion replaces the shard by its converted copy. Only shard-sized
+  // tensors exist at any point.
   at::Tensor shard = at::empty(shard_sizes, options.dtype(steps.front().dtype));
   size_t lo = 0;
   while (lo < steps.size()) {
@@ -2152,11 +2464,12 @@ at::Tensor replayChainOnShard(FakeTensorImpl* fake,
       ++hi;
     }
     const auto run =
-        fusedRunStart(steps, lo, hi, meta.numel(), /*allow_cast=*/false);
+        fusedRunStart(plain, lo, hi, meta.numel(), /*allow_cast=*/false);
     for (size_t i = lo; i < hi; ++i) {
       if (run.has_value() && i == run->rng) {
         applyFusedShardStep(steps[i], tailOf(*run), shard, w, meta.numel());
-        break;  // only pass steps remain in this segment
+        i = run->tail_end - 1;  // pass steps and patches remain
+        continue;
       }
       applyShardStep(steps[i], shard, w, meta.numel());
     }
@@ -2183,7 +2496,8 @@ const char* tailOpName(int32_t op) {
 // (uniform/normal/bernoulli/fill/zero) overwrites the whole tensor, so
 // only the LAST one determines the bits: batched replay can then fill
 // many tensors with ONE kernel launch. Returns nullopt for anything
-// else (pointwise tails, views, cross-tensor deps, explicit
+// else (pointwise tails, live partial-tensor writes — see
+// tensorPatchPlan —, strided views, cross-tensor deps, explicit
 // generators); callers fall back to ordinary materialization.
 std::optional<InitPlan> tensorInitPlan(const at::Tensor& tensor) {
   auto plan = chainPlanImpl(tensor, /*allow_tail=*/false);
@@ -2195,6 +2509,18 @@ std::optional<InitPlan> tensorInitPlan(const at::Tensor& tensor) {
 
 std::optional<ChainPlan> tensorChainPlan(const at::Tensor& tensor) {
   return chainPlanImpl(tensor, fusedInitChainsEnabled());
+}
+
+std::optional<PatchPlan> tensorPatchPlan(const at::Tensor& tensor) {
+  std::vector<PatchStep> patches;
+  auto plan = chainPlanImpl(tensor, fusedInitChainsEnabled(), &patches);
+  if (!plan.has_value()) {
+    return std::nullopt;
+  }
+  PatchPlan out;
+  static_cast<ChainPlan&>(out) = std::move(*plan);
+  out.patches = std::move(patches);
+  return out;
 }
 
 at::Tensor materializeTensorShard(const at::Tensor& tensor,

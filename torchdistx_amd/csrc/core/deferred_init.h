@@ -124,15 +124,47 @@ struct ChainPlan : InitPlan {
 // unplannable, as in tensorInitPlan.
 std::optional<ChainPlan> tensorChainPlan(const at::Tensor& tensor);
 
+// A value step recorded on a contiguous proper sub-range of the tensor
+// (`w[i].zero_()`, `w[:k].normal_(std=s)`): it sets flat elements
+// [lo, lo + len) to what element k - lo of a contiguous len-element tensor
+// gets from the whole-tensor op, and leaves the rest alone.
+struct PatchStep {
+  int64_t lo = 0;
+  int64_t len = 0;
+  InitPlan::Kind kind = InitPlan::Kind::kZero;  // never kFactory
+  double p0 = 0.0;
+  double p1 = 0.0;
+  uint64_t seed = 0;
+  uint64_t offset = 0;
+};
+
+// ChainPlan of the base value step plus the live patches behind it, in
+// application order (later ones overwrite earlier ones).
+struct PatchPlan : ChainPlan {
+  std::vector<PatchStep> patches;
+};
+
+// tensorChainPlan for chains that also hold live patches. tensorInitPlan
+// and tensorChainPlan return nullopt for those (their callers rely on
+// "one value step"); this returns the base plan and the patches. nullopt
+// whenever the chain is unplannable for any other reason, and when an RNG
+// patch coexists with a dtype conversion (it draws at the dtype it was
+// recorded at; slice materialization serves that, a batched plan does
+// not). A constant patch recorded before a conversion carries its value
+// already rounded through the source dtype.
+std::optional<PatchPlan> tensorPatchPlan(const at::Tensor& tensor);
+
 // Slice materialization: materializes indices [start_row, end_row) of
 // the deferred tensor along `dim` WITHOUT materializing the rest,
 // bitwise-equal to the corresponding slice of a full materialization
 // (per device type). dim 0 serves FSDP `Shard(0)` and column-parallel
 // weights; dim 1 serves row-parallel (Megatron-style TP) weights.
 // Requires the tensor's tape to be a "simple init chain" — a factory
-// (empty/zeros/ones/full) followed by whole-tensor in-place init ops
-// (uniform_/normal_/fill_/zero_), aliasing pass-throughs
-// (detach/variable_data) and same-device dtype conversions (`to`, and
+// (empty/zeros/ones/full) followed by in-place init ops
+// (uniform_/normal_/bernoulli_/fill_/zero_) on the whole tensor or on a
+// contiguous sub-range of it reached through view ops (select/slice/
+// narrow/view/reshape/flatten/unflatten/squeeze/unsqueeze), aliasing
+// pass-throughs (detach/variable_data) and same-device dtype conversions (`to`, and
 // the `p.data = p.to(dtype)` that `Module.to(dtype)` records) — which is
 // exactly what module constructors record; throws a descriptive error
 // otherwise so callers can fall back to full materialization. The shard

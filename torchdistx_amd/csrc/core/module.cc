@@ -186,6 +186,51 @@ PYBIND11_MODULE(_C, m) {
      "inside its kernel. None when the chain is not plannable, or has a "
      "tail while fused init chains are switched off.");
 
+  m.def("tensor_patch_plan", [](const at::Tensor& t) -> pybind11::object {
+    auto plan = tdx::tensorPatchPlan(t);
+    if (!plan.has_value()) {
+      return pybind11::none();
+    }
+    static const char* kKinds[] = {"factory", "uniform", "normal",
+                                   "bernoulli", "fill", "zero"};
+    pybind11::dict d;
+    d["kind"] = kKinds[static_cast<int>(plan->kind)];
+    d["p0"] = plan->p0;
+    d["p1"] = plan->p1;
+    d["seed"] = static_cast<int64_t>(plan->seed);
+    d["offset"] = static_cast<int64_t>(plan->offset);
+    d["sizes"] = plan->sizes;
+    d["dtype"] = pybind11::cast(plan->dtype);
+    d["src_dtype"] = srcDtypeObject(*plan);
+    d["device"] = pybind11::cast(plan->device);
+    d["requires_grad"] = plan->requires_grad;
+    pybind11::list tail;
+    for (const tdx::TailOp& op : plan->tail) {
+      tail.append(pybind11::make_tuple(tdx::tailOpName(op.op), op.s0, op.s1));
+    }
+    d["tail"] = tail;
+    pybind11::list patches;
+    for (const tdx::PatchStep& ps : plan->patches) {
+      pybind11::dict pd;
+      pd["lo"] = ps.lo;
+      pd["len"] = ps.len;
+      pd["kind"] = kKinds[static_cast<int>(ps.kind)];
+      pd["p0"] = ps.p0;
+      pd["p1"] = ps.p1;
+      pd["seed"] = static_cast<int64_t>(ps.seed);
+      pd["offset"] = static_cast<int64_t>(ps.offset);
+      patches.append(pd);
+    }
+    d["patches"] = patches;
+    return d;
+  }, "tensor_chain_plan of the base value step plus \"patches\": the value "
+     "steps recorded on contiguous sub-ranges of the tensor behind it "
+     "([{lo, len, kind, p0, p1, seed, offset}, ...], in application "
+     "order), each applied with tdx::patch_box_. tensor_init_plan and "
+     "tensor_chain_plan are None for such chains. None when the chain is "
+     "unplannable for another reason, or when an RNG patch coexists with "
+     "a dtype conversion.");
+
   m.def("materialize_tensor_shard",
         [](const at::Tensor& t, int64_t start_row, int64_t end_row,
            int64_t dim) {

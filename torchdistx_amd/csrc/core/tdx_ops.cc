@@ -542,6 +542,101 @@ at::Tensor& cpu_rng_chain_cast_(at::Tensor& self, at::ScalarType src_dtype,
                                        self.numel(), seed, offset);
 }
 
+// ---- patch: a value step on a contiguous sub-range of the full tensor -----
+// The shard elements whose full-tensor index lies in
+// [patch_lo, patch_lo + patch_len) take the value that element
+// k = g - patch_lo of a contiguous patch_len-element tensor gets from the
+// full-tensor op; every other element is left alone. Only the rows of the
+// box that meet the patch are visited (rowsMeeting). CUDA twin:
+// csrc/hip/init_kernels.hip patch_box_kernel.
+at::Tensor& cpu_patch_box_(at::Tensor& shard, at::IntArrayRef extents,
+                           at::IntArrayRef g_strides, int64_t run_len,
+                           int64_t g_off, int64_t full_numel,
+                           int64_t patch_lo, int64_t patch_len, int64_t dist,
+                           double p0, double p1, std::optional<int64_t> seed,
+                           std::optional<int64_t> offset) {
+  TORCH_CHECK(shard.is_contiguous(),
+              "tdx CPU init requires contiguous tensors");
+  const char* err =
+      checkBoxArgs(extents.data(), extents.size(), g_strides.data(),
+                   g_strides.size(), run_len, g_off, shard.numel(),
+                   full_numel);
+  TORCH_CHECK(err == nullptr, "patch_box: ", err);
+  err = checkPatchArgs(patch_lo, patch_len, full_numel, dist,
+                       seed.has_value(), offset.has_value());
+  TORCH_CHECK(err == nullptr, "patch_box: ", err);
+  TORCH_CHECK(dist != 1 || p1 >= 0.0,
+              "normal_ expects std >= 0.0, but found std=", p1);
+  TORCH_CHECK(dist != 2 || (0.0 <= p0 && p0 <= 1.0),
+              "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
+  TORCH_CHECK(shard.scalar_type() == at::kFloat ||
+                  shard.scalar_type() == at::kBFloat16 ||
+                  shard.scalar_type() == at::kHalf,
+              "tdx patch kernel supports float32/bf16/fp16, got ",
+              shard.scalar_type());
+  BoxGeometry geo;
+  geo.g_off = g_off;
+  geo.run_len = run_len;
+  geo.levels = static_cast<int32_t>(extents.size());
+  for (int l = 0; l < geo.levels; ++l) {
+    geo.extent[l] = extents[l];
+    geo.g_stride[l] = g_strides[l];
+  }
+  const int64_t patch_hi = patch_lo + patch_len;
+  const RowRange rows = rowsMeeting(geo, patch_lo, patch_hi);
+  if (rows.count() == 0) {
+    return shard;
+  }
+  const auto s = static_cast<uint64_t>(seed.value_or(0));
+  const auto o = static_cast<uint64_t>(offset.value_or(0));
+  const float a = static_cast<float>(p0);
+  const float b = dist == 0 ? static_cast<float>(p1 - p0)
+                            : (dist == 1 ? static_cast<float>(p1) : 0.0f);
+  at::Tensor flat = shard.view({-1});
+  auto run = [&](auto* out) {
+    using T = std::remove_pointer_t<decltype(out)>;
+    for (int64_t r = rows.first; r < rows.last; ++r) {
+      const int64_t rs = geo.rowStart(r);
+      const int64_t ga = std::max(rs, patch_lo);
+      const int64_t gb = std::min(rs + run_len, patch_hi);
+      const int64_t at_shard = r * run_len + (ga - rs);
+      switch (dist) {
+        case 0:
+          cpuPhiloxRange<T, RngKind::kUniform>(out + at_shard, ga - patch_lo,
+                                               gb - patch_lo, a, b, s, o);
+          break;
+        case 1:
+          cpuPhiloxRange<T, RngKind::kNormal>(out + at_shard, ga - patch_lo,
+                                              gb - patch_lo, a, b, s, o);
+          break;
+        case 2:
+          cpuPhiloxRange<T, RngKind::kBernoulli>(out + at_shard,
+                                                 ga - patch_lo, gb - patch_lo,
+                                                 a, b, s, o);
+          break;
+        case 3:
+          flat.narrow(0, at_shard, gb - ga).fill_(p0);
+          break;
+        default:
+          flat.narrow(0, at_shard, gb - ga).zero_();
+          break;
+      }
+    }
+  };
+  switch (shard.scalar_type()) {
+    case at::kFloat:
+      run(shard.data_ptr<float>());
+      break;
+    case at::kBFloat16:
+      run(shard.data_ptr<at::BFloat16>());
+      break;
+    default:
+      run(shard.data_ptr<at::Half>());
+      break;
+  }
+  return shard;
+}
+
 TORCH_LIBRARY(tdx, m) {
   m.def(
       "uniform_(Tensor(a!) self, float from=0., float to=1., *, "
@@ -615,6 +710,16 @@ TORCH_LIBRARY(tdx, m) {
       "int run_len, int g_off, int dist, float p0, float p1, "
       "int[] tail_ops, float[] tail_s0, float[] tail_s1, int full_numel, "
       "int seed, int offset) -> Tensor(a!)");
+  // A value step on the contiguous range [patch_lo, patch_lo + patch_len)
+  // of the full tensor, applied to the part of it the box holds. Geometry
+  // as for rng_box_ (a flat range or window is the one-level box it is);
+  // dist: 0 uniform, 1 normal, 2 bernoulli, 3 fill (p0), 4 zero. The
+  // values are those of the full-tensor op run on a contiguous
+  // patch_len-element tensor of the shard's dtype with that seed/offset.
+  m.def(
+      "patch_box_(Tensor(a!) shard, int[] extents, int[] g_strides, "
+      "int run_len, int g_off, int full_numel, int patch_lo, int patch_len, "
+      "int dist, float p0, float p1, int? seed, int? offset) -> Tensor(a!)");
 }
 
 TORCH_LIBRARY_IMPL(tdx, CPU, m) {
@@ -633,6 +738,7 @@ TORCH_LIBRARY_IMPL(tdx, CPU, m) {
   m.impl("rng_chain_", cpu_rng_chain_);
   m.impl("rng_chain_shard_win_", cpu_rng_chain_shard_win_);
   m.impl("rng_box_", cpu_rng_box_);
+  m.impl("patch_box_", cpu_patch_box_);
   m.impl("rng_chain_cast_", cpu_rng_chain_cast_);
   m.impl("rng_chain_cast_shard_win_", cpu_rng_chain_cast_shard_win_);
 }

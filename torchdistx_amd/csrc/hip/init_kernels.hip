@@ -1758,6 +1758,271 @@ at::Tensor& tdx_rng_box_(at::Tensor& shard, at::IntArrayRef extents,
   return shard;
 }
 
+// ---------------------------------------------------------------------------
+// Patch kernel (tdx::patch_box_): a value step recorded on a contiguous
+// sub-range [lo, hi) of the full tensor (`w[i].zero_()`,
+// `w[:k].normal_()`), applied to the part of it a box holds. The rows of
+// the box that meet the patch are one contiguous row range, found on the
+// host (rowsMeeting); the kernel walks only those, so its work is the
+// intersection plus the two edge rows, whatever the shard's or the
+// patch's size.
+//
+// A work item is one (row, view group) pair: `slots` items per row, the
+// most 16-byte groups of the patch VIEW a row can meet. Item s of a row
+// is group k0 / kElems + s of the view, k0 being the row's first view
+// element; items past the row's last group do nothing. The group's values
+// come from rngGroupValues keyed by the VIEW group index, so they are the
+// full-tensor kernels' values for a contiguous patch_len-element tensor;
+// the lanes inside row and patch are stored, as one 16-byte store when the
+// group is whole and its destination aligned, element by element
+// otherwise. The constant kinds store the scalar narrowed as fill_kernel
+// narrows it.
+// ---------------------------------------------------------------------------
+
+// Geometry in ELEMENTS. Levels are outermost first; only levels 1.. are
+// divided by, as in BoxArgs.
+template <typename IdxT>
+struct PatchArgs {
+  int64_t g_off;
+  int64_t gs[kMaxBoxLevels];
+  int64_t run_len;
+  int64_t lo, hi;     // the patch, in full-tensor elements
+  int64_t row_first;  // first row that meets the patch
+  IdxT ext[kMaxBoxLevels];
+  IdxT slots;
+  int32_t levels;
+  uint32_t slots_magic, slots_shift;
+  uint32_t ext_magic[kMaxBoxLevels - 1];
+  uint32_t ext_shift[kMaxBoxLevels - 1];
+};
+
+enum class PatchKind { kUniform, kNormal, kBernoulli, kConst };
+
+template <typename T, PatchKind kKind, typename IdxT, bool kMagic>
+__global__ void patch_box_kernel(T* __restrict__ out,
+                                 PatchArgs<IdxT> p,
+                                 IdxT n_work,
+                                 float a,
+                                 float b,
+                                 uint64_t seed,
+                                 uint64_t offset) {
+  constexpr int kElems = VecTraits<T>::kElems;
+  using Vec = typename VecTraits<T>::Vec;
+  const IdxT stride = static_cast<IdxT>(gridDim.x) * blockDim.x;
+  for (IdxT w = blockIdx.x * static_cast<IdxT>(blockDim.x) + threadIdx.x;
+       w < n_work; w += stride) {
+    const IdxT rel =
+        boxDiv<IdxT, kMagic>(w, p.slots, p.slots_magic, p.slots_shift);
+    const IdxT slot = w - rel * p.slots;
+    const int64_t row = p.row_first + static_cast<int64_t>(rel);
+    // First full-tensor element of the row (BoxGeometry::rowStart).
+    IdxT rem = static_cast<IdxT>(row);
+    int64_t rs = p.g_off;
+#pragma unroll
+    for (int l = kMaxBoxLevels - 1; l >= 1; --l) {
+      if (l < p.levels) {
+        const IdxT q = boxDiv<IdxT, kMagic>(rem, p.ext[l], p.ext_magic[l - 1],
+                                            p.ext_shift[l - 1]);
+        rs += static_cast<int64_t>(rem - q * p.ext[l]) * p.gs[l];
+        rem = q;
+      }
+    }
+    rs += static_cast<int64_t>(rem) * p.gs[0];
+    // Row ∩ patch in view elements [k0, k1); non-empty for these rows.
+    const int64_t ga = rs > p.lo ? rs : p.lo;
+    const int64_t gb = rs + p.run_len < p.hi ? rs + p.run_len : p.hi;
+    const int64_t k0 = ga - p.lo;
+    const int64_t k1 = gb - p.lo;
+    const int64_t g = k0 / kElems + static_cast<int64_t>(slot);
+    const int64_t kb = g * kElems;
+    if (kb >= k1) {
+      continue;
+    }
+    // Shard index of the group's lane 0 (before the row's start when the
+    // group begins left of it; only in-range lanes are addressed).
+    const int64_t i0 = row * p.run_len + (kb + p.lo - rs);
+    T vals_t[kElems];
+    if constexpr (kKind == PatchKind::kConst) {
+      const T value = from_float<T>(a);
+#pragma unroll
+      for (int e = 0; e < kElems; ++e) {
+        vals_t[e] = value;
+      }
+    } else {
+      constexpr Dist kDist = kKind == PatchKind::kUniform
+                                 ? Dist::kUniform
+                                 : (kKind == PatchKind::kNormal
+                                        ? Dist::kNormal
+                                        : Dist::kBernoulli);
+      float vals[kElems];
+      rngGroupValues<T, kDist>(static_cast<uint64_t>(g), a, b, seed, offset,
+                               vals);
+#pragma unroll
+      for (int e = 0; e < kElems; ++e) {
+        vals_t[e] = from_float<T>(vals[e]);
+      }
+    }
+    const bool whole = kb >= k0 && kb + kElems <= k1;
+    if (whole && reinterpret_cast<uintptr_t>(out + i0) % 16 == 0) {
+      Vec v;
+      T* vp = reinterpret_cast<T*>(&v);
+#pragma unroll
+      for (int e = 0; e < kElems; ++e) {
+        vp[e] = vals_t[e];
+      }
+      *reinterpret_cast<Vec*>(out + i0) = v;
+    } else {
+#pragma unroll
+      for (int e = 0; e < kElems; ++e) {
+        const int64_t k = kb + e;
+        if (k >= k0 && k < k1) {
+          out[i0 + e] = vals_t[e];
+        }
+      }
+    }
+  }
+}
+
+template <PatchKind kKind>
+void launchPatchBox(at::Tensor& shard, const BoxGeometry& geo,
+                    const RowRange& rows, int64_t patch_lo, int64_t patch_len,
+                    float a, float b, uint64_t seed, uint64_t offset) {
+  auto stream = at::cuda::getCurrentCUDAStream();
+  auto launch = [&](auto type_tag) {
+    using T = decltype(type_tag);
+    constexpr int64_t kElems = VecTraits<T>::kElems;
+    // The most view groups an interval of run_len elements can touch,
+    // and never more than the view has.
+    const int64_t slots =
+        std::min((geo.run_len + kElems - 2) / kElems + 1,
+                 (patch_len + kElems - 1) / kElems);
+    const int64_t n_work = rows.count() * slots;
+    auto launch_idx = [&](auto idx_tag, auto magic_tag) {
+      using IdxT = decltype(idx_tag);
+      constexpr bool kMagic = decltype(magic_tag)::value;
+      PatchArgs<IdxT> p{};
+      p.g_off = geo.g_off;
+      p.run_len = geo.run_len;
+      p.lo = patch_lo;
+      p.hi = patch_lo + patch_len;
+      p.row_first = rows.first;
+      p.levels = geo.levels;
+      p.slots = static_cast<IdxT>(slots);
+      for (int l = 0; l < kMaxBoxLevels; ++l) {
+        p.gs[l] = 0;
+        p.ext[l] = 1;
+      }
+      for (int l = 0; l < geo.levels; ++l) {
+        p.gs[l] = geo.g_stride[l];
+        p.ext[l] = static_cast<IdxT>(geo.extent[l]);
+      }
+      if constexpr (kMagic) {
+        const MagicDiv32 sd = makeMagicDiv32(static_cast<uint32_t>(slots));
+        p.slots_magic = sd.magic;
+        p.slots_shift = sd.shift;
+        for (int l = 1; l < kMaxBoxLevels; ++l) {
+          const MagicDiv32 ed =
+              makeMagicDiv32(static_cast<uint32_t>(p.ext[l]));
+          p.ext_magic[l - 1] = ed.magic;
+          p.ext_shift[l - 1] = ed.shift;
+        }
+      }
+      hipLaunchKernelGGL((patch_box_kernel<T, kKind, IdxT, kMagic>),
+                         dim3(numBlocks(n_work)), dim3(kBlock), 0,
+                         stream.stream(),
+                         reinterpret_cast<T*>(shard.data_ptr()), p,
+                         static_cast<IdxT>(n_work), a, b, seed, offset);
+      C10_HIP_KERNEL_LAUNCH_CHECK();
+    };
+    // The multiply-shift division is exact below 2^31: both the work
+    // index and the row index must stay under it.
+    if (n_work > std::numeric_limits<int32_t>::max() ||
+        geo.rows() > std::numeric_limits<int32_t>::max()) {
+      launch_idx(int64_t{}, std::false_type{});
+    } else {
+      launch_idx(uint32_t{}, std::true_type{});
+    }
+  };
+  switch (shard.scalar_type()) {
+    case at::kFloat:
+      launch(float{});
+      break;
+    case at::kBFloat16:
+      launch(__hip_bfloat16{});
+      break;
+    default:
+      launch(__half{});
+      break;
+  }
+}
+
+at::Tensor& tdx_patch_box_(at::Tensor& shard, at::IntArrayRef extents,
+                           at::IntArrayRef g_strides, int64_t run_len,
+                           int64_t g_off, int64_t full_numel,
+                           int64_t patch_lo, int64_t patch_len, int64_t dist,
+                           double p0, double p1, std::optional<int64_t> seed,
+                           std::optional<int64_t> offset) {
+  TORCH_CHECK(shard.is_contiguous(),
+              "tdx shard kernels require contiguous tensors");
+  const char* err =
+      checkBoxArgs(extents.data(), extents.size(), g_strides.data(),
+                   g_strides.size(), run_len, g_off, shard.numel(),
+                   full_numel);
+  TORCH_CHECK(err == nullptr, "patch_box: ", err);
+  err = checkPatchArgs(patch_lo, patch_len, full_numel, dist,
+                       seed.has_value(), offset.has_value());
+  TORCH_CHECK(err == nullptr, "patch_box: ", err);
+  TORCH_CHECK(dist != 1 || p1 >= 0.0,
+              "normal_ expects std >= 0.0, but found std=", p1);
+  TORCH_CHECK(dist != 2 || (0.0 <= p0 && p0 <= 1.0),
+              "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
+  TORCH_CHECK(shard.scalar_type() == at::kFloat ||
+                  shard.scalar_type() == at::kBFloat16 ||
+                  shard.scalar_type() == at::kHalf,
+              "tdx patch kernel supports float32/bf16/fp16, got ",
+              shard.scalar_type());
+  BoxGeometry geo;
+  geo.g_off = g_off;
+  geo.run_len = run_len;
+  geo.levels = static_cast<int32_t>(extents.size());
+  for (int l = 0; l < geo.levels; ++l) {
+    geo.extent[l] = extents[l];
+    geo.g_stride[l] = g_strides[l];
+  }
+  const RowRange rows = rowsMeeting(geo, patch_lo, patch_lo + patch_len);
+  if (rows.count() == 0) {
+    return shard;  // the patch misses the box (or one of them is empty)
+  }
+  const auto s = static_cast<uint64_t>(seed.value_or(0));
+  const auto o = static_cast<uint64_t>(offset.value_or(0));
+  const float a = static_cast<float>(p0);
+  switch (dist) {
+    case 0:
+      launchPatchBox<PatchKind::kUniform>(shard, geo, rows, patch_lo,
+                                          patch_len, a,
+                                          static_cast<float>(p1 - p0), s, o);
+      break;
+    case 1:
+      launchPatchBox<PatchKind::kNormal>(shard, geo, rows, patch_lo,
+                                         patch_len, a, static_cast<float>(p1),
+                                         s, o);
+      break;
+    case 2:
+      launchPatchBox<PatchKind::kBernoulli>(shard, geo, rows, patch_lo,
+                                            patch_len, a, 0.0f, s, o);
+      break;
+    case 3:
+      launchPatchBox<PatchKind::kConst>(shard, geo, rows, patch_lo, patch_len,
+                                        a, 0.0f, 0, 0);
+      break;
+    default:
+      launchPatchBox<PatchKind::kConst>(shard, geo, rows, patch_lo, patch_len,
+                                        0.0f, 0.0f, 0, 0);
+      break;
+  }
+  return shard;
+}
+
 at::Tensor& tdx_fill_(at::Tensor& self, const at::Scalar& value) {
   TORCH_CHECK(self.is_contiguous(),
               "tdx init kernels require contiguous tensors");
@@ -2523,6 +2788,7 @@ TORCH_LIBRARY_IMPL(tdx, CUDA, m) {
   m.impl("rng_chain_", tdx_rng_chain_);
   m.impl("rng_chain_shard_win_", tdx_rng_chain_shard_win_);
   m.impl("rng_box_", tdx_rng_box_);
+  m.impl("patch_box_", tdx_patch_box_);
   m.impl("rng_chain_cast_", tdx_rng_chain_cast_);
   m.impl("rng_chain_cast_shard_win_", tdx_rng_chain_cast_shard_win_);
 }

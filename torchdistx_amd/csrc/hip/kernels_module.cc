@@ -58,6 +58,7 @@ PYBIND11_MODULE(_K, m) {
   m.def("has_fused_chains", [] { return true; });
   m.def("has_box_kernel", [] { return true; });
   m.def("has_cast_chains", [] { return true; });
+  m.def("has_patch_kernel", [] { return true; });
 
   m.def("batched_init_", &tdx::batched_init_launch,
         pybind11::arg("tensors"), pybind11::arg("dists"),

@@ -239,7 +239,18 @@ def _batched_fill(entries, device=None) -> list:
     one batched kernel launch and swaps the module slots; returns the
     entries that must go through ordinary replay instead. Used by
     :func:`materialize_module_batched` and the distributed shard path.
-    ``device`` overrides the plans' target device (retargeting)."""
+    ``device`` overrides the plans' target device (retargeting).
+
+    A chain whose init also overwrites contiguous sub-ranges of the tensor
+    (``nn.Embedding(padding_idx=i)``, a fused weight initialized by parts)
+    has no chain plan; ``_C.tensor_patch_plan`` gives its base value step,
+    which joins the batch like any other plan, and its patches. After the
+    batched launch each patch is one ``tdx::patch_box_`` call on the flat
+    output, on the same stream. Patches are rare (one or two per model), so
+    a launch each is cheaper than teaching the batched kernel about them.
+    Under retargeting a normal patch recorded for another device sends the
+    tensor to ordinary replay, as a tail does (the normal transform is per
+    device); uniform, bernoulli and constant patches do not."""
     import torch
 
     from torchdistx_amd import _kernels
@@ -271,8 +282,13 @@ def _batched_fill(entries, device=None) -> list:
         hasattr(_kernels._K, "has_cast_chains")
         and _kernels._K.has_cast_chains()
     )
+    patch_kernel = (
+        hasattr(_kernels._K, "has_patch_kernel")
+        and _kernels._K.has_patch_kernel()
+    )
     batch = {"t": [], "dist": [], "p0": [], "p1": [], "seed": [],
              "offset": [], "tail": [], "src": [], "entry": []}
+    patched = []  # (out, patches): applied after the batched launches
     fallback = []
     seen = {}  # id(fake) -> out: tied params must share ONE allocation
     for entry in entries:
@@ -284,6 +300,12 @@ def _batched_fill(entries, device=None) -> list:
             plan = _C.tensor_chain_plan(tensor)
         else:
             plan = _C.tensor_init_plan(tensor)
+        patches = []
+        if plan is None and patch_kernel:
+            plan = _C.tensor_patch_plan(tensor)
+            if plan is not None and plan["tail"] and not fused:
+                plan = None
+            patches = plan["patches"] if plan is not None else []
         tail = plan.get("tail", []) if plan is not None else []
         src_dtype = plan.get("src_dtype") if plan is not None else None
         if (
@@ -298,7 +320,7 @@ def _batched_fill(entries, device=None) -> list:
             # A tail recorded on another device replays there: the
             # uniform bits match across devices, erfinv's need not.
             or (
-                tail
+                (tail or any(p["kind"] == "normal" for p in patches))
                 and device is not None
                 and not _same_device(plan["device"], device)
             )
@@ -323,6 +345,8 @@ def _batched_fill(entries, device=None) -> list:
             batch["src"].append(src_dtype)
         # kind == "factory": allocate-only, matching aten::empty replay.
         batch["entry"].append((entry, out))
+        if patches:
+            patched.append((out, patches))
 
     if batch["t"] and any(d is not None for d in batch["src"]):
         # Tensors with a conversion fill in a second launch of their own
@@ -348,6 +372,16 @@ def _batched_fill(entries, device=None) -> list:
             batch["t"], batch["dist"], batch["p0"], batch["p1"],
             batch["seed"], batch["offset"],
         )
+    for out, patches in patched:
+        n = out.numel()
+        flat = out.view(-1)
+        for p in patches:
+            rng = p["kind"] in ("uniform", "normal", "bernoulli")
+            torch.ops.tdx.patch_box_(
+                flat, [1], [n], n, 0, n, p["lo"], p["len"],
+                _DIST_CODE[p["kind"]], p["p0"], p["p1"],
+                p["seed"] if rng else None, p["offset"] if rng else None,
+            )
     for (submodule, key, tensor, is_param), out in batch["entry"]:
         if is_param:
             if out.is_leaf and out.requires_grad != tensor.requires_grad:

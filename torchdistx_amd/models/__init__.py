@@ -8,6 +8,7 @@ from torchdistx_amd.models.configs import (  # noqa: F401
     TINY,
     TINY_GPT2,
     TINY_MOE,
+    TINY_PADDED,
     TransformerConfig,
 )
 from torchdistx_amd.models.transformer import (  # noqa: F401

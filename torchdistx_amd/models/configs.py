@@ -30,6 +30,11 @@ class TransformerConfig:
     # bias), which records the empty -> uniform_ tape shape of unmodified
     # user models.
     init: str = "fast"
+    # Row of the token embedding kept at zero (nn.Embedding's padding_idx):
+    # the init records a whole-tensor normal_ and then a zero fill of that
+    # one row, the partial-tensor write slice materialization serves with
+    # tdx::patch_box_. None (every stock config) records no such write.
+    padding_idx: Optional[int] = None
 
     @property
     def n_params(self) -> int:
@@ -98,6 +103,19 @@ TINY_MOE = TransformerConfig(
     max_seq_len=64,
     moe_num_experts=4,
     moe_top_k=2,
+)
+
+# TINY with a padding row in the token embedding (a pad-token model).
+TINY_PADDED = TransformerConfig(
+    name="tiny-padded",
+    vocab_size=128,
+    dim=64,
+    n_layers=2,
+    n_heads=4,
+    n_kv_heads=2,
+    ffn_hidden=128,
+    max_seq_len=64,
+    padding_idx=3,
 )
 
 GPT2_XL = TransformerConfig(
@@ -171,6 +189,7 @@ CONFIGS = {
         TINY,
         TINY_GPT2,
         TINY_MOE,
+        TINY_PADDED,
         GPT2_XL,
         LLAMA3_8B,
         LLAMA3_70B,

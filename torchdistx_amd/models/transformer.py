@@ -61,10 +61,12 @@ def _linear(d_in: int, d_out: int, bias: bool = False) -> nn.Linear:
     return InitLinear(d_in, d_out, bias=bias)
 
 
-def _embedding(num: int, dim: int) -> nn.Embedding:
+def _embedding(
+    num: int, dim: int, padding_idx: Optional[int] = None
+) -> nn.Embedding:
     if _stock_init():
-        return nn.Embedding(num, dim)
-    return InitEmbedding(num, dim)
+        return nn.Embedding(num, dim, padding_idx=padding_idx)
+    return InitEmbedding(num, dim, padding_idx=padding_idx)
 
 
 class RMSNorm(nn.Module):
@@ -204,7 +206,7 @@ class TransformerLM(nn.Module):
     def __init__(self, cfg: TransformerConfig):
         super().__init__()
         self.cfg = cfg
-        self.tok_emb = _embedding(cfg.vocab_size, cfg.dim)
+        self.tok_emb = _embedding(cfg.vocab_size, cfg.dim, cfg.padding_idx)
         if cfg.rope:
             self.pos_emb = None
             # RoPE rotates half the head dim; cache covers head_dim/2 freqs.
