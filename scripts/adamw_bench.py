@@ -73,3 +73,68 @@ def bench_many_small(use_batched, n_tensors=512, numel=16384, steps=10):
 for name, batched in (("per-tensor fused", False), ("batched", True)):
     ms = bench_many_small(batched)
     print(f"512x16k params, {name}: {ms:8.2f} ms/step")
+
+
+# ---------------------------------------------------------------------------
+# Block-scaled fp8 states (csrc/hip/anyprecision_adamw_q8.hip): bf16 p/g,
+# e4m3fn momentum, e5m2 variance, without and with bf16 Kahan, next to the
+# fused flagship layout measured the same way in the same process. Each
+# figure is the median of `repeats` timings of `steps` steps.
+# ---------------------------------------------------------------------------
+
+E4M3, E5M2 = torch.float8_e4m3fn, torch.float8_e5m2
+SCALES = 8.0 / 256  # two fp32 scales read and written per 256 elements
+CONFIGS = {
+    # name: (momentum, variance, kahan, bytes per element)
+    "flagship fused (f32 m, bf16 v, kahan)": (
+        torch.float32, torch.bfloat16, True, 22.0),
+    "flagship fused (f32 m, bf16 v, no kahan)": (
+        torch.float32, torch.bfloat16, False, 18.0),
+    "q8 (e4m3 m, e5m2 v, no kahan)": (E4M3, E5M2, False, 10.0 + SCALES),
+    "q8 (e4m3 m, e5m2 v, kahan)": (E4M3, E5M2, True, 14.0 + SCALES),
+}
+
+
+def timed(opt, steps, repeats):
+    opt.step()  # state + warm-up
+    opt.step()
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            opt.step()
+        torch.cuda.synchronize()
+        out.append((time.perf_counter() - t0) / steps * 1e3)
+    out.sort()
+    return out[len(out) // 2], out[0], out[-1]
+
+
+def bench_layout(sizes, config, steps=10, repeats=5):
+    m_dt, v_dt, kahan, _ = config
+    torch.manual_seed(2)
+    params = [
+        torch.nn.Parameter(
+            torch.randn(k, device="cuda", dtype=torch.bfloat16))
+        for k in sizes
+    ]
+    opt = AnyPrecisionAdamW(
+        params, lr=1e-3, weight_decay=0.01, use_kahan_summation=kahan,
+        momentum_dtype=m_dt, variance_dtype=v_dt,
+        compensation_buffer_dtype=torch.bfloat16, use_fused=True,
+    )
+    for p in params:
+        p.grad = torch.randn_like(p)
+    result = timed(opt, steps, repeats)
+    assert opt._fused_steps == len(params) * (2 + steps * repeats)
+    return result
+
+
+for label, sizes in (("2^28 elements", [n]), ("512x16k", [16384] * 512)):
+    # The flagship layouts twice: the second pass is their run-to-run
+    # spread under the same conditions.
+    for name in list(CONFIGS) + list(CONFIGS)[:2]:
+        med, lo, hi = bench_layout(sizes, CONFIGS[name])
+        tb = CONFIGS[name][3] * sum(sizes) / (med * 1e-3) / 1e12
+        print(f"{label}, {name}: median {med:8.3f} ms/step "
+              f"(min {lo:.3f}, max {hi:.3f})  effective {tb:5.2f} TB/s")

@@ -7,6 +7,7 @@ import torch
 def has_init_kernels() -> bool: ...
 def has_anyprecision_adamw() -> bool: ...
 def has_anyprecision_adamw_batched() -> bool: ...
+def has_anyprecision_adamw_q8() -> bool: ...
 def has_batched_init() -> bool: ...
 def has_fused_chains() -> bool: ...
 def has_box_kernel() -> bool: ...
@@ -31,6 +32,22 @@ def anyprecision_adamw_batched_(
     grads: List[torch.Tensor],
     exp_avgs: List[torch.Tensor],
     exp_avg_sqs: List[torch.Tensor],
+    compensations: List[Optional[torch.Tensor]],
+    lr: float,
+    beta1: float,
+    beta2: float,
+    eps: float,
+    weight_decay: float,
+    step_sizes: List[float],
+    bias_correction2_sqrts: List[float],
+) -> None: ...
+def anyprecision_adamw_q8_(
+    params: List[torch.Tensor],
+    grads: List[torch.Tensor],
+    exp_avgs: List[torch.Tensor],
+    exp_avg_scales: List[Optional[torch.Tensor]],
+    exp_avg_sqs: List[torch.Tensor],
+    exp_avg_sq_scales: List[Optional[torch.Tensor]],
     compensations: List[Optional[torch.Tensor]],
     lr: float,
     beta1: float,

@@ -88,3 +88,49 @@ def anyprecision_adamw_batched_(
         step_sizes,
         bias_correction2_sqrts,
     )
+
+
+def has_anyprecision_adamw_q8() -> bool:
+    return (
+        _HAS_K
+        and torch.cuda.is_available()
+        and hasattr(_K, "has_anyprecision_adamw_q8")
+    )
+
+
+def anyprecision_adamw_q8_(
+    params,
+    grads,
+    exp_avgs,
+    exp_avg_scales,
+    exp_avg_sqs,
+    exp_avg_sq_scales,
+    compensations,
+    lr,
+    beta1,
+    beta2,
+    eps,
+    weight_decay,
+    step_sizes,
+    bias_correction2_sqrts,
+):
+    """One kernel launch updating every listed parameter whose exp_avg
+    and/or exp_avg_sq are block-scaled fp8 (see
+    csrc/hip/anyprecision_adamw_q8.hip; a scale entry is None for a state
+    that is not fp8)."""
+    _K.anyprecision_adamw_q8_(
+        params,
+        [g.contiguous() for g in grads],
+        exp_avgs,
+        exp_avg_scales,
+        exp_avg_sqs,
+        exp_avg_sq_scales,
+        compensations,
+        lr,
+        beta1,
+        beta2,
+        eps,
+        weight_decay,
+        step_sizes,
+        bias_correction2_sqrts,
+    )

@@ -23,10 +23,12 @@
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
 
+#include "adamw_device.h"
+
 namespace tdx {
 namespace {
 
-enum class DT : int { kF32 = 0, kBF16 = 1, kF16 = 2 };
+using namespace adamw_device;  // DT, roundBarrier, lerpMomentum
 
 __device__ __forceinline__ float loadf(const void* p, DT dt, int64_t i) {
   switch (dt) {
@@ -37,15 +39,6 @@ __device__ __forceinline__ float loadf(const void* p, DT dt, int64_t i) {
     default:
       return __half2float(static_cast<const __half*>(p)[i]);
   }
-}
-
-// Pins the f32 rounding step before narrowing conversions, so every
-// code path (generic, vectorized, batched) rounds identically — the
-// compiler otherwise fuses fma+convert (v_fma_mix*) in some shapes only
-// (see init_kernels.hip from_float).
-__device__ __forceinline__ float roundBarrier(float v) {
-  asm volatile("" : "+v"(v));
-  return v;
 }
 
 __device__ __forceinline__ void storef(void* p, DT dt, int64_t i, float v) {
@@ -61,20 +54,6 @@ __device__ __forceinline__ void storef(void* p, DT dt, int64_t i, float v) {
       static_cast<__half*>(p)[i] = __float2half(v);
       break;
   }
-}
-
-// m + w * (g - m), rounded once. Where g is close to -m * (1 - w) / w
-// (g ~ -9 m at beta1 = 0.9) the result cancels, and the fp32 rounding
-// errors of g - m and of the product, a few 2^-24 (|m| + |g|), would be
-// thousands of ulps of it; the update is step_size * exp_avg / denom and
-// would inherit them, which next to a parameter much smaller than the
-// update is far outside the fp32 rounding of that parameter. Two fp32
-// operands differ and multiply exactly enough in fp64 (full rate on
-// CDNA), so the momentum alone is formed there: five VALU ops.
-__device__ __forceinline__ float lerpMomentum(float m, float g, float w) {
-  const double md = m;
-  return static_cast<float>(
-      fma(static_cast<double>(w), static_cast<double>(g) - md, md));
 }
 
 // Vector packs: 8 elements per thread per iteration, 16-byte accesses for

@@ -46,6 +46,22 @@ void anyprecision_adamw_batched_step(
     std::vector<double> step_sizes,
     std::vector<double> bias_correction2_sqrts);
 
+void anyprecision_adamw_q8_step(
+    std::vector<at::Tensor> params,
+    std::vector<at::Tensor> grads,
+    std::vector<at::Tensor> exp_avgs,
+    std::vector<std::optional<at::Tensor>> exp_avg_scales,
+    std::vector<at::Tensor> exp_avg_sqs,
+    std::vector<std::optional<at::Tensor>> exp_avg_sq_scales,
+    std::vector<std::optional<at::Tensor>> compensations,
+    double lr,
+    double beta1,
+    double beta2,
+    double eps,
+    double weight_decay,
+    std::vector<double> step_sizes,
+    std::vector<double> bias_correction2_sqrts);
+
 }  // namespace tdx
 
 PYBIND11_MODULE(_K, m) {
@@ -54,6 +70,7 @@ PYBIND11_MODULE(_K, m) {
   m.def("has_init_kernels", [] { return true; });
   m.def("has_anyprecision_adamw", [] { return true; });
   m.def("has_anyprecision_adamw_batched", [] { return true; });
+  m.def("has_anyprecision_adamw_q8", [] { return true; });
   m.def("has_batched_init", [] { return true; });
   m.def("has_fused_chains", [] { return true; });
   m.def("has_box_kernel", [] { return true; });
@@ -89,6 +106,19 @@ PYBIND11_MODULE(_K, m) {
         pybind11::arg("bias_correction2_sqrts"),
         "One-launch AdamW update for a whole list of parameters (kahan "
         "optional per tensor via the compensations list).");
+
+  m.def("anyprecision_adamw_q8_", &tdx::anyprecision_adamw_q8_step,
+        pybind11::arg("params"), pybind11::arg("grads"),
+        pybind11::arg("exp_avgs"), pybind11::arg("exp_avg_scales"),
+        pybind11::arg("exp_avg_sqs"), pybind11::arg("exp_avg_sq_scales"),
+        pybind11::arg("compensations"), pybind11::arg("lr"),
+        pybind11::arg("beta1"), pybind11::arg("beta2"), pybind11::arg("eps"),
+        pybind11::arg("weight_decay"), pybind11::arg("step_sizes"),
+        pybind11::arg("bias_correction2_sqrts"),
+        "One-launch AdamW update for a list of parameters whose exp_avg "
+        "and/or exp_avg_sq are block-scaled fp8 (float8_e4m3fn or "
+        "float8_e5m2 codes plus one fp32 power-of-two scale per 256 "
+        "elements; the scale entry is None for a state that is not fp8).");
 
   m.def(
       "anyprecision_adamw_",

@@ -39,6 +39,43 @@ def _local_view(t):
 _BATCH_MAX_NUMEL = 1 << 20
 
 
+# Block-scaled fp8 optimizer states (docs/anyprecision_adamw.md, "8-bit
+# states"): codes in the state tensor, one fp32 power-of-two scale per
+# _Q8_BLOCK consecutive elements in state["<name>_scale"].
+_Q8_DTYPES = (torch.float8_e4m3fn, torch.float8_e5m2)
+_Q8_BLOCK = 256
+_FP8_DTYPES = _Q8_DTYPES + tuple(
+    getattr(torch, name)
+    for name in ("float8_e4m3fnuz", "float8_e5m2fnuz", "float8_e8m0fnu")
+    if hasattr(torch, name)
+)
+
+
+def _check_state_dtypes(momentum_dtype, variance_dtype, compensation_dtype):
+    for name, dtype in (("momentum_dtype", momentum_dtype),
+                        ("variance_dtype", variance_dtype)):
+        if dtype in _FP8_DTYPES and dtype not in _Q8_DTYPES:
+            raise ValueError(
+                f"{name}={dtype} is not supported: the 8-bit optimizer "
+                "states are the OCP formats torch.float8_e4m3fn and "
+                "torch.float8_e5m2 (gfx950 converts these natively; the "
+                "fnuz formats are not supported)"
+            )
+    if compensation_dtype in _FP8_DTYPES:
+        raise ValueError(
+            f"compensation_buffer_dtype={compensation_dtype} is not "
+            "supported: the Kahan compensation buffer must be float32, "
+            "bfloat16 or float16 (fp8 is for exp_avg and exp_avg_sq only)"
+        )
+
+
+def _q8_scale(state_tensor):
+    """Fresh scales for a zero-initialized fp8 state: 1.0 per quant block."""
+    n_blocks = -(-state_tensor.numel() // _Q8_BLOCK)
+    return torch.ones(n_blocks, dtype=torch.float32,
+                      device=state_tensor.device)
+
+
 def _kernel_loaded() -> bool:
     try:
         from torchdistx_amd import _kernels
@@ -46,6 +83,23 @@ def _kernel_loaded() -> bool:
         return _kernels.has_anyprecision_adamw()
     except Exception:
         return False
+
+
+def _q8_kernel_loaded() -> bool:
+    try:
+        from torchdistx_amd import _kernels
+
+        return _kernels.has_anyprecision_adamw_q8()
+    except Exception:
+        return False
+
+
+def _is_dtensor(t) -> bool:
+    try:
+        from torch.distributed.tensor import DTensor
+    except ImportError:
+        return False
+    return isinstance(t, DTensor)
 
 
 def _fused_step_available(p: torch.Tensor) -> bool:
@@ -76,6 +130,12 @@ class AnyPrecisionAdamW(Optimizer):
             (default: False).
         momentum_dtype: dtype of ``exp_avg`` (default: torch.float32).
         variance_dtype: dtype of ``exp_avg_sq`` (default: torch.bfloat16).
+            Either may also be ``torch.float8_e4m3fn`` or
+            ``torch.float8_e5m2``: the state then holds fp8 codes next to
+            one fp32 power-of-two scale per 256 elements
+            (``state["exp_avg_scale"]`` / ``state["exp_avg_sq_scale"]``),
+            and exists on the fused GPU path only — ``step`` raises
+            ``RuntimeError`` where that path cannot run.
         compensation_buffer_dtype: dtype of the Kahan compensation buffer
             (default: torch.bfloat16).
         use_fused: True forces the fused single-kernel CDNA4 step and
@@ -112,7 +172,23 @@ class AnyPrecisionAdamW(Optimizer):
             variance_dtype=variance_dtype,
             compensation_buffer_dtype=compensation_buffer_dtype,
         )
+        _check_state_dtypes(
+            momentum_dtype, variance_dtype, compensation_buffer_dtype
+        )
         super().__init__(params, defaults)
+        for group in self.param_groups:
+            _check_state_dtypes(
+                group["momentum_dtype"],
+                group["variance_dtype"],
+                group["compensation_buffer_dtype"],
+            )
+            for p in group["params"]:
+                if p.dtype in _FP8_DTYPES:
+                    raise ValueError(
+                        f"parameter dtype {p.dtype} is not supported: fp8 "
+                        "is for the optimizer states exp_avg and "
+                        "exp_avg_sq only"
+                    )
         self.use_fused = use_fused
         # Diagnostic: number of parameter updates that took the fused
         # CDNA4 kernel (lets tests and benchmarks assert the fast path
@@ -139,6 +215,51 @@ class AnyPrecisionAdamW(Optimizer):
                     state["compensation"] = state["compensation"].to(
                         group["compensation_buffer_dtype"]
                     )
+        # Block-scaled fp8 states come back bit for bit: codes and fp32
+        # scales are taken from the incoming dict itself, not from the base
+        # class's detour through the parameter dtype (an fp16 parameter
+        # cannot even represent a scale of 2^-100).
+        by_index = {}
+        for saved_group, group in zip(state_dict["param_groups"],
+                                      self.param_groups):
+            by_index.update(zip(saved_group["params"], group["params"]))
+        for index, saved in state_dict["state"].items():
+            state = self.state.get(by_index.get(index))
+            if not state:
+                continue
+            for key in ("exp_avg", "exp_avg_sq"):
+                if key not in saved or saved[key].dtype not in _Q8_DTYPES:
+                    continue
+                for k, dtype in ((key, saved[key].dtype),
+                                 (key + "_scale", torch.float32)):
+                    state[k] = saved[k].detach().to(
+                        device=state[k].device, dtype=dtype, copy=True)
+
+    def _check_q8_can_run(self, p, kernel_loaded):
+        """fp8 states exist on the fused path only (torch has no fp8
+        ``lerp_``/``addcmul_``, and an eager emulation would be a second
+        definition of the format): name why it cannot run."""
+        reason = None
+        if self.use_fused is False:
+            reason = "use_fused=False forbids the fused step"
+        elif _is_dtensor(p):
+            reason = ("the parameter is a DTensor, and a per-local-shard "
+                      "scale tensor has no DTensor placement yet")
+        elif p.device.type != "cuda":
+            reason = f"the parameter is on {p.device.type}, not on a GPU"
+        elif not kernel_loaded:
+            reason = ("the kernel extension torchdistx_amd._K (with "
+                      "anyprecision_adamw_q8_) is not loaded")
+        elif torch.utils._python_dispatch.is_traceable_wrapper_subclass(p):
+            reason = "the parameter is a storage-less wrapper subclass"
+        elif not p.is_contiguous():
+            reason = "the parameter is non-contiguous"
+        if reason is not None:
+            raise RuntimeError(
+                "fp8 optimizer states (momentum_dtype/variance_dtype = "
+                "float8_e4m3fn/float8_e5m2) need the fused "
+                f"AnyPrecisionAdamW step, but {reason}"
+            )
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -163,6 +284,12 @@ class AnyPrecisionAdamW(Optimizer):
             # launch overhead would otherwise dominate the small ones.
             batch = {k: [] for k in
                      ("p", "g", "m", "v", "c", "step_size", "bc2")}
+            # A group with an fp8 state takes the block-scaled kernel for
+            # every parameter, whatever its size, in one launch.
+            q8 = momentum_dtype in _Q8_DTYPES or variance_dtype in _Q8_DTYPES
+            if q8:
+                batch["ms"], batch["vs"] = [], []
+                q8_kernel = _q8_kernel_loaded()
 
             for p in group["params"]:
                 if p.grad is None:
@@ -171,6 +298,9 @@ class AnyPrecisionAdamW(Optimizer):
                     raise RuntimeError(
                         "AnyPrecisionAdamW does not support sparse gradients"
                     )
+
+                if q8:
+                    self._check_q8_can_run(p, q8_kernel)
 
                 state = self.state[p]
                 if len(state) == 0:
@@ -181,6 +311,13 @@ class AnyPrecisionAdamW(Optimizer):
                         state["compensation"] = torch.zeros_like(
                             p, dtype=compensation_dtype
                         )
+                    if q8:
+                        if momentum_dtype in _Q8_DTYPES:
+                            state["exp_avg_scale"] = _q8_scale(
+                                state["exp_avg"])
+                        if variance_dtype in _Q8_DTYPES:
+                            state["exp_avg_sq_scale"] = _q8_scale(
+                                state["exp_avg_sq"])
 
                 state["step"] += 1
                 step = state["step"].item()
@@ -202,8 +339,9 @@ class AnyPrecisionAdamW(Optimizer):
                 v_l = _local_view(exp_avg_sq)
                 c_l = _local_view(state["compensation"]) if use_kahan else None
                 can_fuse = (
-                    self.use_fused is not False
-                    and _fused_step_available(p)
+                    # (_check_q8_can_run has covered the first two.)
+                    (q8 or (self.use_fused is not False
+                            and _fused_step_available(p)))
                     and p_l.is_contiguous()
                     and g_l.is_contiguous()
                     and m_l.is_contiguous()
@@ -213,6 +351,25 @@ class AnyPrecisionAdamW(Optimizer):
                     and m_l.numel() == p_l.numel()
                     and v_l.numel() == p_l.numel()
                 )
+                if q8:
+                    if not can_fuse:
+                        raise RuntimeError(
+                            "fp8 optimizer states need the fused "
+                            "AnyPrecisionAdamW step, which cannot run for "
+                            "this parameter: its gradient or states are "
+                            "non-contiguous or mismatched in size"
+                        )
+                    self._fused_steps += 1
+                    batch["p"].append(p_l)
+                    batch["g"].append(g_l)
+                    batch["m"].append(m_l)
+                    batch["ms"].append(state.get("exp_avg_scale"))
+                    batch["v"].append(v_l)
+                    batch["vs"].append(state.get("exp_avg_sq_scale"))
+                    batch["c"].append(c_l)
+                    batch["step_size"].append(step_size)
+                    batch["bc2"].append(bias_correction2_sqrt)
+                    continue
                 if self.use_fused is True and not can_fuse:
                     raise RuntimeError(
                         "use_fused=True, but the fused AnyPrecisionAdamW "
@@ -285,7 +442,26 @@ class AnyPrecisionAdamW(Optimizer):
                         exp_avg.to(p.dtype), denom.to(p.dtype), value=-step_size
                     )
 
-            if batch["p"]:
+            if batch["p"] and q8:
+                from torchdistx_amd import _kernels
+
+                _kernels.anyprecision_adamw_q8_(
+                    batch["p"],
+                    batch["g"],
+                    batch["m"],
+                    batch["ms"],
+                    batch["v"],
+                    batch["vs"],
+                    batch["c"],
+                    lr,
+                    beta1,
+                    beta2,
+                    eps,
+                    weight_decay,
+                    batch["step_size"],
+                    batch["bc2"],
+                )
+            elif batch["p"]:
                 from torchdistx_amd import _kernels
 
                 _kernels.anyprecision_adamw_batched_(
