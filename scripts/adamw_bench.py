@@ -1,6 +1,10 @@
 """A/B of the AnyPrecisionAdamW step on GPU: eager op-sequence vs fused
 CDNA4 kernel, on the flagship dtype layout (bf16 params/grad/variance/comp,
-fp32 momentum, Kahan on)."""
+fp32 momentum, Kahan on).
+
+Modes (arguments; default both): "step" is the A/Bs of the step kernels,
+"clip" compares clip_grad_norm_ followed by the fused step with the fused
+max_grad_norm step and times the gradient norm kernels alone."""
 import sys, os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import time
 
@@ -9,6 +13,8 @@ import torch
 from torchdistx_amd.optimizers import AnyPrecisionAdamW
 
 assert torch.cuda.is_available()
+MODES = sys.argv[1:] or ["step", "clip"]
+assert set(MODES) <= {"step", "clip"}, MODES
 n = 1 << 28  # 268M params (~0.5 GB bf16)
 
 
@@ -33,7 +39,7 @@ def bench(use_fused, steps=10):
     return dt * 1e3, tbps
 
 
-for name, fused in (("eager", False), ("fused", True)):
+for name, fused in (("eager", False), ("fused", True)) * ("step" in MODES):
     ms, tb = bench(fused)
     print(f"{name}: {ms:8.2f} ms/step  effective {tb:5.2f} TB/s")
 
@@ -70,7 +76,8 @@ def bench_many_small(use_batched, n_tensors=512, numel=16384, steps=10):
         apo._BATCH_MAX_NUMEL = saved
 
 
-for name, batched in (("per-tensor fused", False), ("batched", True)):
+for name, batched in ((("per-tensor fused", False), ("batched", True))
+                      * ("step" in MODES)):
     ms = bench_many_small(batched)
     print(f"512x16k params, {name}: {ms:8.2f} ms/step")
 
@@ -130,7 +137,9 @@ def bench_layout(sizes, config, steps=10, repeats=5):
     return result
 
 
-for label, sizes in (("2^28 elements", [n]), ("512x16k", [16384] * 512)):
+SHAPES = (("2^28 elements", [n]), ("512x16k", [16384] * 512))
+
+for label, sizes in SHAPES * ("step" in MODES):
     # The flagship layouts twice: the second pass is their run-to-run
     # spread under the same conditions.
     for name in list(CONFIGS) + list(CONFIGS)[:2]:
@@ -138,3 +147,90 @@ for label, sizes in (("2^28 elements", [n]), ("512x16k", [16384] * 512)):
         tb = CONFIGS[name][3] * sum(sizes) / (med * 1e-3) / 1e12
         print(f"{label}, {name}: median {med:8.3f} ms/step "
               f"(min {lo:.3f}, max {hi:.3f})  effective {tb:5.2f} TB/s")
+
+
+# ---------------------------------------------------------------------------
+# Gradient clipping (csrc/hip/grad_norm.hip), flagship Kahan layout, bf16
+# gradients of norm sqrt(numel) clipped to 1.0:
+#   (a) torch.nn.utils.clip_grad_norm_, then the fused step;
+#   (b) AnyPrecisionAdamW(max_grad_norm=1.0), fused.
+# Windows of (a), (b) and (a) again alternate; the two (a) columns are the
+# run-to-run spread. Then the norm call alone (both kernels and the table
+# copy, timed from the host around a synchronise) against a device copy of
+# the same tensor, which moves twice the bytes.
+# ---------------------------------------------------------------------------
+
+
+def windows(fns, steps=10, repeats=5):
+    """Median, min and max ms/call of each fn; windows alternate."""
+    for fn in fns:
+        fn()
+        fn()
+    out = [[] for _ in fns]
+    for _ in range(repeats):
+        for times, fn in zip(out, fns):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                fn()
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) / steps * 1e3)
+    return [(sorted(t)[len(t) // 2], min(t), max(t)) for t in out]
+
+
+def clip_setup(sizes, max_grad_norm):
+    torch.manual_seed(3)
+    params = [
+        torch.nn.Parameter(
+            torch.randn(k, device="cuda", dtype=torch.bfloat16))
+        for k in sizes
+    ]
+    opt = AnyPrecisionAdamW(
+        params, lr=1e-3, weight_decay=0.01, use_kahan_summation=True,
+        momentum_dtype=torch.float32, variance_dtype=torch.bfloat16,
+        compensation_buffer_dtype=torch.bfloat16, use_fused=True,
+        max_grad_norm=max_grad_norm,
+    )
+    for p in params:
+        p.grad = torch.randn_like(p)
+    return params, opt
+
+
+def bench_clip(label, sizes):
+    from torchdistx_amd import _kernels
+
+    pa, opt_a = clip_setup(sizes, None)
+    pb, opt_b = clip_setup(sizes, 1.0)
+    pc, opt_c = clip_setup(sizes, None)
+
+    def torch_clip(params, opt):
+        def fn():
+            torch.nn.utils.clip_grad_norm_(params, 1.0)
+            opt.step()
+        return fn
+
+    names = ("(a) clip_grad_norm_ + fused step", "(b) max_grad_norm fused",
+             "(a) again")
+    results = windows(
+        [torch_clip(pa, opt_a), opt_b.step, torch_clip(pc, opt_c)])
+    for name, (med, lo, hi) in zip(names, results):
+        print(f"{label}, {name}: median {med:8.3f} ms/step "
+              f"(min {lo:.3f}, max {hi:.3f})")
+    assert opt_b.grad_clip_coef < 1
+
+    grads = [p.grad for p in pb]
+    out = torch.empty(2, device="cuda")
+    src = torch.cat([g.reshape(-1) for g in grads])
+    dst = torch.empty_like(src)
+    nbytes = src.numel() * src.element_size()
+    (norm, _, _), (copy, _, _) = windows(
+        [lambda: _kernels.grad_norm_clip_coef_(grads, 1.0, out),
+         lambda: dst.copy_(src)], steps=20)
+    print(f"{label}, norm call alone: median {norm:8.3f} ms, "
+          f"{nbytes / (norm * 1e-3) / 1e12:5.2f} TB/s read; "
+          f"device copy: {copy:8.3f} ms, "
+          f"{2 * nbytes / (copy * 1e-3) / 1e12:5.2f} TB/s read+write")
+
+
+for label, sizes in SHAPES * ("clip" in MODES):
+    bench_clip(label, sizes)

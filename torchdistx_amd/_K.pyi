@@ -8,6 +8,7 @@ def has_init_kernels() -> bool: ...
 def has_anyprecision_adamw() -> bool: ...
 def has_anyprecision_adamw_batched() -> bool: ...
 def has_anyprecision_adamw_q8() -> bool: ...
+def has_grad_norm() -> bool: ...
 def has_batched_init() -> bool: ...
 def has_fused_chains() -> bool: ...
 def has_box_kernel() -> bool: ...
@@ -26,6 +27,7 @@ def anyprecision_adamw_(
     weight_decay: float,
     step_size: float,
     bias_correction2_sqrt: float,
+    grad_scale: Optional[torch.Tensor] = None,
 ) -> None: ...
 def anyprecision_adamw_batched_(
     params: List[torch.Tensor],
@@ -40,6 +42,7 @@ def anyprecision_adamw_batched_(
     weight_decay: float,
     step_sizes: List[float],
     bias_correction2_sqrts: List[float],
+    grad_scale: Optional[torch.Tensor] = None,
 ) -> None: ...
 def anyprecision_adamw_q8_(
     params: List[torch.Tensor],
@@ -56,7 +59,14 @@ def anyprecision_adamw_q8_(
     weight_decay: float,
     step_sizes: List[float],
     bias_correction2_sqrts: List[float],
+    grad_scale: Optional[torch.Tensor] = None,
 ) -> None: ...
+def grad_norm_clip_coef_(
+    grads: List[torch.Tensor],
+    max_norm: float,
+    out: torch.Tensor,
+) -> None: ...
+def grad_norm_grid_cap() -> int: ...
 def batched_init_(
     tensors: List[torch.Tensor],
     dists: List[int],

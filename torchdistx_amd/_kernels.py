@@ -41,6 +41,7 @@ def anyprecision_adamw_(
     weight_decay,
     step_size,
     bias_correction2_sqrt,
+    grad_scale=None,
 ):
     _K.anyprecision_adamw_(
         param,
@@ -55,6 +56,7 @@ def anyprecision_adamw_(
         weight_decay,
         step_size,
         bias_correction2_sqrt,
+        grad_scale,
     )
 
 
@@ -71,6 +73,7 @@ def anyprecision_adamw_batched_(
     weight_decay,
     step_sizes,
     bias_correction2_sqrts,
+    grad_scale=None,
 ):
     """One kernel launch updating every listed parameter (see
     csrc/hip/anyprecision_adamw.hip, adamw_batched_kernel)."""
@@ -87,6 +90,7 @@ def anyprecision_adamw_batched_(
         weight_decay,
         step_sizes,
         bias_correction2_sqrts,
+        grad_scale,
     )
 
 
@@ -113,6 +117,7 @@ def anyprecision_adamw_q8_(
     weight_decay,
     step_sizes,
     bias_correction2_sqrts,
+    grad_scale=None,
 ):
     """One kernel launch updating every listed parameter whose exp_avg
     and/or exp_avg_sq are block-scaled fp8 (see
@@ -133,4 +138,22 @@ def anyprecision_adamw_q8_(
         weight_decay,
         step_sizes,
         bias_correction2_sqrts,
+        grad_scale,
     )
+
+
+def has_grad_norm() -> bool:
+    return (
+        _HAS_K
+        and torch.cuda.is_available()
+        and hasattr(_K, "has_grad_norm")
+    )
+
+
+def grad_norm_clip_coef_(grads, max_norm, out):
+    """Global L2 norm of the listed gradients, accumulated in fp64, into
+    out[0] and the clip_grad_norm_ coefficient min(max_norm / (norm + 1e-6),
+    1) into out[1] (see csrc/hip/grad_norm.hip). out: 2-element float32
+    tensor on the gradients' device; nothing returns to the host. The step
+    wrappers above take out[1:2] as grad_scale."""
+    _K.grad_norm_clip_coef_(grads, max_norm, out)

@@ -26,9 +26,14 @@
 #include "adamw_device.h"
 
 namespace tdx {
+
+// grad_norm.hip
+const float* gradScalePtr(const std::optional<at::Tensor>& grad_scale,
+                          const at::Tensor& param);
+
 namespace {
 
-using namespace adamw_device;  // DT, roundBarrier, lerpMomentum
+using namespace adamw_device;  // DT, roundBarrier, lerpMomentum, scaleGrad
 
 __device__ __forceinline__ float loadf(const void* p, DT dt, int64_t i) {
   switch (dt) {
@@ -110,13 +115,16 @@ struct AdamWScalars {
   float one_minus_beta1;
   float one_minus_beta2;
   float decay;  // 1 - lr * weight_decay
+  // nullptr, or one fp32 every gradient is multiplied by as it is loaded
+  // (the clip coefficient grad_norm.hip leaves on the device).
+  const float* grad_scale;
 };
 
 // Vectorized fused step: 8 elements per thread per grid-stride iteration,
 // full 16-byte (bf16/fp16) or 2x16-byte (fp32) accesses per tensor. The
 // update math is identical to the generic kernel below.
 template <typename Tp, typename Tg, typename Tm, typename Tv, typename Tc,
-          bool kKahan>
+          bool kKahan, bool kScaled>
 __global__ void adamw_vec_kernel(Tp* __restrict__ param,
                                  const Tg* __restrict__ grad,
                                  Tm* __restrict__ exp_avg,
@@ -124,6 +132,12 @@ __global__ void adamw_vec_kernel(Tp* __restrict__ param,
                                  Tc* __restrict__ compensation,
                                  AdamWScalars s) {
   const int64_t n_groups = s.n / 8;  // full groups; tail by generic kernel
+  // kScaled == (s.grad_scale != nullptr); the unscaled instantiation is
+  // the kernel as it was before the scale existed.
+  float grad_scale = 1.0f;
+  if constexpr (kScaled) {
+    grad_scale = *s.grad_scale;
+  }
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   for (int64_t g = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
        g < n_groups; g += stride) {
@@ -131,6 +145,16 @@ __global__ void adamw_vec_kernel(Tp* __restrict__ param,
     float p[8], gr[8], m[8], v[8];
     load8(param, base, p);
     load8(grad, base, gr);
+    // The barrier hides where the gradient came from, in both variants:
+    // the arithmetic below then vectorizes and contracts identically in
+    // them, so a scale of exactly 1 gives the unscaled kernel's bits.
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      if constexpr (kScaled) {
+        gr[j] = scaleGrad(gr[j], grad_scale);
+      }
+      gr[j] = roundBarrier(gr[j]);
+    }
     load8(exp_avg, base, m);
     load8(exp_avg_sq, base, v);
     float c[8];
@@ -207,17 +231,26 @@ struct AdamWArgs {
   float one_minus_beta1;  // host-computed, see AdamWScalars
   float one_minus_beta2;
   float decay;
+  const float* grad_scale;  // see AdamWScalars
 };
 
+template <bool kScaled>  // == (args.grad_scale != nullptr)
 __global__ void anyprecision_adamw_kernel(AdamWArgs args) {
   const int64_t stride = static_cast<int64_t>(gridDim.x) * blockDim.x;
   const bool kahan = args.compensation != nullptr;
+  float grad_scale = 1.0f;
+  if constexpr (kScaled) {
+    grad_scale = *args.grad_scale;
+  }
 
   for (int64_t i = args.i0 +
            blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
        i < args.n; i += stride) {
     float p = loadf(args.param, args.dt_param, i);
-    const float g = loadf(args.grad, args.dt_grad, i);
+    float g = loadf(args.grad, args.dt_grad, i);
+    if constexpr (kScaled) {
+      g = scaleGrad(g, grad_scale);
+    }
     float m = loadf(args.exp_avg, args.dt_m, i);
     float v = loadf(args.exp_avg_sq, args.dt_v, i);
 
@@ -282,8 +315,11 @@ int64_t tryLaunchVec(const AdamWArgs& args, int grid, int block,
   AdamWScalars s{n_full,         args.lr,       args.beta1,
                  args.beta2,     args.eps,      args.weight_decay,
                  args.step_size, args.bias_correction2_sqrt,
-                 args.one_minus_beta1, args.one_minus_beta2, args.decay};
+                 args.one_minus_beta1, args.one_minus_beta2, args.decay,
+                 args.grad_scale};
   bool launched = false;
+  auto launch = [&](auto scaled_tag) {
+  constexpr bool kScaled = decltype(scaled_tag)::value;
   dispatch2(args.dt_param, [&](auto tp) {
     using Tp = decltype(tp);
     dispatch2(args.dt_grad, [&](auto tg) {
@@ -294,7 +330,7 @@ int64_t tryLaunchVec(const AdamWArgs& args, int grid, int block,
           using Tv = decltype(tv);
           if (args.compensation == nullptr) {
             hipLaunchKernelGGL(
-                (adamw_vec_kernel<Tp, Tg, Tm, Tv, float, false>), dim3(grid),
+                (adamw_vec_kernel<Tp, Tg, Tm, Tv, float, false, kScaled>), dim3(grid),
                 dim3(block), 0, stream,
                 static_cast<Tp*>(args.param),
                 static_cast<const Tg*>(args.grad),
@@ -305,7 +341,7 @@ int64_t tryLaunchVec(const AdamWArgs& args, int grid, int block,
             dispatch2(args.dt_c, [&](auto tc) {
               using Tc = decltype(tc);
               hipLaunchKernelGGL(
-                  (adamw_vec_kernel<Tp, Tg, Tm, Tv, Tc, true>), dim3(grid),
+                  (adamw_vec_kernel<Tp, Tg, Tm, Tv, Tc, true, kScaled>), dim3(grid),
                   dim3(block), 0, stream,
                   static_cast<Tp*>(args.param),
                   static_cast<const Tg*>(args.grad),
@@ -319,6 +355,12 @@ int64_t tryLaunchVec(const AdamWArgs& args, int grid, int block,
       });
     });
   });
+  };
+  if (args.grad_scale != nullptr) {
+    launch(std::true_type{});
+  } else {
+    launch(std::false_type{});
+  }
   return launched ? n_full : 0;
 }
 
@@ -351,14 +393,20 @@ struct BatchHeader {
   int64_t total_vblocks;
   float lr, beta1, beta2, eps, weight_decay;
   float one_minus_beta1, one_minus_beta2, decay;  // see AdamWScalars
+  const float* grad_scale;                        // see AdamWScalars
 };
 
 // blob layout: int64 prefix[n_tensors] then BatchTensorMeta[n_tensors].
+template <bool kScaled>  // == (h.grad_scale != nullptr)
 __global__ void adamw_batched_kernel(const uint8_t* __restrict__ blob,
                                      BatchHeader h) {
   const int64_t* prefix = reinterpret_cast<const int64_t*>(blob);
   const BatchTensorMeta* metas = reinterpret_cast<const BatchTensorMeta*>(
       blob + sizeof(int64_t) * h.n_tensors);
+  float grad_scale = 1.0f;
+  if constexpr (kScaled) {
+    grad_scale = *h.grad_scale;
+  }
 
   for (int64_t vb = blockIdx.x; vb < h.total_vblocks; vb += gridDim.x) {
     // Largest t with prefix[t] <= vb.
@@ -381,7 +429,10 @@ __global__ void adamw_batched_kernel(const uint8_t* __restrict__ blob,
         break;
       }
       float p = loadf(mt.param, static_cast<DT>(mt.dt_param), i);
-      const float g = loadf(mt.grad, static_cast<DT>(mt.dt_grad), i);
+      float g = loadf(mt.grad, static_cast<DT>(mt.dt_grad), i);
+      if constexpr (kScaled) {
+        g = scaleGrad(g, grad_scale);
+      }
       float m = loadf(mt.exp_avg, static_cast<DT>(mt.dt_m), i);
       float v = loadf(mt.exp_avg_sq, static_cast<DT>(mt.dt_v), i);
 
@@ -440,7 +491,8 @@ void anyprecision_adamw_step(at::Tensor& param,
                              double eps,
                              double weight_decay,
                              double step_size,
-                             double bias_correction2_sqrt) {
+                             double bias_correction2_sqrt,
+                             std::optional<at::Tensor> grad_scale) {
   TORCH_CHECK(param.is_cuda() && grad.is_cuda(),
               "fused AnyPrecisionAdamW requires GPU tensors");
   const at::Tensor* checked[] = {
@@ -487,6 +539,7 @@ void anyprecision_adamw_step(at::Tensor& param,
   args.one_minus_beta1 = static_cast<float>(1.0 - beta1);
   args.one_minus_beta2 = static_cast<float>(1.0 - beta2);
   args.decay = static_cast<float>(1.0 - lr * weight_decay);
+  args.grad_scale = gradScalePtr(grad_scale, param);
 
   const int block = 256;
   const int grid = static_cast<int>(
@@ -497,8 +550,10 @@ void anyprecision_adamw_step(at::Tensor& param,
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
   if (args.i0 < args.n) {
-    hipLaunchKernelGGL(anyprecision_adamw_kernel, dim3(grid), dim3(block), 0,
-                       stream.stream(), args);
+    hipLaunchKernelGGL(args.grad_scale != nullptr
+                           ? anyprecision_adamw_kernel<true>
+                           : anyprecision_adamw_kernel<false>,
+                       dim3(grid), dim3(block), 0, stream.stream(), args);
     C10_HIP_KERNEL_LAUNCH_CHECK();
   }
 }
@@ -515,7 +570,8 @@ void anyprecision_adamw_batched_step(
     double eps,
     double weight_decay,
     std::vector<double> step_sizes,
-    std::vector<double> bias_correction2_sqrts) {
+    std::vector<double> bias_correction2_sqrts,
+    std::optional<at::Tensor> grad_scale) {
   const size_t n_tensors = params.size();
   TORCH_CHECK(n_tensors > 0, "batched AdamW: empty tensor list");
   TORCH_CHECK(grads.size() == n_tensors && exp_avgs.size() == n_tensors &&
@@ -601,12 +657,14 @@ void anyprecision_adamw_batched_step(
   h.one_minus_beta1 = static_cast<float>(1.0 - beta1);
   h.one_minus_beta2 = static_cast<float>(1.0 - beta2);
   h.decay = static_cast<float>(1.0 - lr * weight_decay);
+  h.grad_scale = gradScalePtr(grad_scale, params[0]);
 
   const int grid =
       static_cast<int>(std::min<int64_t>(total_vblocks, 16384));
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(adamw_batched_kernel, dim3(grid), dim3(256), 0,
-                     stream.stream(),
+  hipLaunchKernelGGL(h.grad_scale != nullptr ? adamw_batched_kernel<true>
+                                             : adamw_batched_kernel<false>,
+                     dim3(grid), dim3(256), 0, stream.stream(),
                      static_cast<const uint8_t*>(dev_blob.const_data_ptr()),
                      h);
   C10_HIP_KERNEL_LAUNCH_CHECK();

@@ -46,9 +46,14 @@
 #include "adamw_device.h"
 
 namespace tdx {
+
+// grad_norm.hip
+const float* gradScalePtr(const std::optional<at::Tensor>& grad_scale,
+                          const at::Tensor& param);
+
 namespace {
 
-using namespace adamw_device;  // DT, roundBarrier, lerpMomentum
+using namespace adamw_device;  // DT, roundBarrier, lerpMomentum, ...
 
 // Operand dtype tags: DT's three, then the two fp8 formats.
 constexpr int kTagE4M3 = 3;
@@ -73,28 +78,7 @@ __device__ __forceinline__ float fmaxOf(int tag) {
 }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float asFloat(uint32_t b) {
-  return __builtin_bit_cast(float, b);
-}
-__device__ __forceinline__ uint32_t asBits(float v) {
-  return __builtin_bit_cast(uint32_t, v);
-}
-
-__device__ __forceinline__ float loadOne(const void* p, int tag, int64_t i) {
-  if (tag == static_cast<int>(DT::kF32)) {
-    return static_cast<const float*>(p)[i];
-  }
-  if (tag == static_cast<int>(DT::kBF16)) {
-    return asFloat(
-        static_cast<uint32_t>(static_cast<const uint16_t*>(p)[i]) << 16);
-  }
-  return static_cast<float>(static_cast<const _Float16*>(p)[i]);
-}
 
 // One round-to-nearest-even conversion of the fp32 value, as storef.
 __device__ __forceinline__ void storeOne(void* p, int tag, int64_t i,
@@ -149,39 +133,7 @@ __device__ __forceinline__ void load8Fp8(const uint8_t* p, int tag,
   }
 }
 
-__device__ __forceinline__ void load8Plain(const void* p, int tag, int64_t e0,
-                                           int count, bool wide, float* out) {
-  if (!wide) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      out[j] = j < count ? loadOne(p, tag, e0 + j) : 0.0f;
-    }
-    return;
-  }
-  if (tag == static_cast<int>(DT::kF32)) {
-    const f32x4* q =
-        reinterpret_cast<const f32x4*>(static_cast<const float*>(p) + e0);
-    const f32x4 a = q[0];
-    const f32x4 b = q[1];
-    out[0] = a.x; out[1] = a.y; out[2] = a.z; out[3] = a.w;
-    out[4] = b.x; out[5] = b.y; out[6] = b.z; out[7] = b.w;
-    return;
-  }
-  const u32x4 pk = *reinterpret_cast<const u32x4*>(
-      static_cast<const uint16_t*>(p) + e0);
-  const uint32_t w[4] = {pk.x, pk.y, pk.z, pk.w};
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    if (tag == static_cast<int>(DT::kBF16)) {
-      out[2 * k] = asFloat(w[k] << 16);
-      out[2 * k + 1] = asFloat(w[k] & 0xffff0000u);
-    } else {
-      const half2v h = __builtin_bit_cast(half2v, w[k]);
-      out[2 * k] = static_cast<float>(h.x);
-      out[2 * k + 1] = static_cast<float>(h.y);
-    }
-  }
-}
+// (load8Plain, for the operands that are not fp8: adamw_device.h.)
 
 // ---------------------------------------------------------------------------
 // Stores
@@ -420,6 +372,7 @@ struct Q8Header {
   int64_t total_vblocks;
   float beta2, eps, weight_decay;
   float one_minus_beta1, one_minus_beta2, decay;  // host-narrowed
+  const float* grad_scale;  // nullptr, or one fp32 every gradient is scaled by
 };
 
 __device__ __forceinline__ bool alignedTo(const void* p, uintptr_t bytes) {
@@ -427,12 +380,17 @@ __device__ __forceinline__ bool alignedTo(const void* p, uintptr_t bytes) {
 }
 
 // blob layout: int64 prefix[n_tensors] then Q8TensorMeta[n_tensors].
+template <bool kScaled>  // == (h.grad_scale != nullptr)
 __global__ __launch_bounds__(kQ8Threads) void adamw_q8_kernel(
     const uint8_t* __restrict__ blob, Q8Header h) {
   const int64_t* prefix = reinterpret_cast<const int64_t*>(blob);
   const Q8TensorMeta* metas = reinterpret_cast<const Q8TensorMeta*>(
       blob + sizeof(int64_t) * h.n_tensors);
   const bool first_of_half_wave = (threadIdx.x & 31) == 0;
+  float grad_scale = 1.0f;
+  if constexpr (kScaled) {
+    grad_scale = *h.grad_scale;
+  }
 
   for (int64_t vb = blockIdx.x; vb < h.total_vblocks; vb += gridDim.x) {
     // Largest t with prefix[t] <= vb.
@@ -467,6 +425,12 @@ __global__ __launch_bounds__(kQ8Threads) void adamw_q8_kernel(
     float p[8], g[8], m[8], v[8], c[8];
     load8Plain(mt.param, mt.dt_param, e0, count, wide_p, p);
     load8Plain(mt.grad, mt.dt_grad, e0, count, wide_g, g);
+    if constexpr (kScaled) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        g[j] = scaleGrad(g[j], grad_scale);
+      }
+    }
     if (m_q8) {
       const float s = halfWaveBroadcast(
           scale_lane ? mt.exp_avg_scale[qb] : 1.0f);
@@ -586,7 +550,8 @@ void anyprecision_adamw_q8_step(
     double eps,
     double weight_decay,
     std::vector<double> step_sizes,
-    std::vector<double> bias_correction2_sqrts) {
+    std::vector<double> bias_correction2_sqrts,
+    std::optional<at::Tensor> grad_scale) {
   const size_t n_tensors = params.size();
   TORCH_CHECK(n_tensors > 0, "q8 AdamW: empty tensor list");
   TORCH_CHECK(grads.size() == n_tensors && exp_avgs.size() == n_tensors &&
@@ -693,12 +658,14 @@ void anyprecision_adamw_q8_step(
   h.one_minus_beta1 = static_cast<float>(1.0 - beta1);
   h.one_minus_beta2 = static_cast<float>(1.0 - beta2);
   h.decay = static_cast<float>(1.0 - lr * weight_decay);
+  h.grad_scale = gradScalePtr(grad_scale, params[0]);
 
   const int grid =
       static_cast<int>(std::min<int64_t>(total_vblocks, 16384));
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(adamw_q8_kernel, dim3(grid), dim3(kQ8Threads), 0,
-                     stream.stream(),
+  hipLaunchKernelGGL(h.grad_scale != nullptr ? adamw_q8_kernel<true>
+                                             : adamw_q8_kernel<false>,
+                     dim3(grid), dim3(kQ8Threads), 0, stream.stream(),
                      static_cast<const uint8_t*>(dev_blob.const_data_ptr()),
                      h);
   C10_HIP_KERNEL_LAUNCH_CHECK();

@@ -18,7 +18,8 @@ void anyprecision_adamw_step(at::Tensor& param,
                              double eps,
                              double weight_decay,
                              double step_size,
-                             double bias_correction2_sqrt);
+                             double bias_correction2_sqrt,
+                             std::optional<at::Tensor> grad_scale);
 
 void batched_init_launch(std::vector<at::Tensor> tensors,
                          std::vector<int64_t> dists,
@@ -44,7 +45,8 @@ void anyprecision_adamw_batched_step(
     double eps,
     double weight_decay,
     std::vector<double> step_sizes,
-    std::vector<double> bias_correction2_sqrts);
+    std::vector<double> bias_correction2_sqrts,
+    std::optional<at::Tensor> grad_scale);
 
 void anyprecision_adamw_q8_step(
     std::vector<at::Tensor> params,
@@ -60,7 +62,13 @@ void anyprecision_adamw_q8_step(
     double eps,
     double weight_decay,
     std::vector<double> step_sizes,
-    std::vector<double> bias_correction2_sqrts);
+    std::vector<double> bias_correction2_sqrts,
+    std::optional<at::Tensor> grad_scale);
+
+void grad_norm_clip_coef(std::vector<at::Tensor> grads, double max_norm,
+                         at::Tensor& out);
+
+int64_t grad_norm_grid_cap();
 
 }  // namespace tdx
 
@@ -71,6 +79,7 @@ PYBIND11_MODULE(_K, m) {
   m.def("has_anyprecision_adamw", [] { return true; });
   m.def("has_anyprecision_adamw_batched", [] { return true; });
   m.def("has_anyprecision_adamw_q8", [] { return true; });
+  m.def("has_grad_norm", [] { return true; });
   m.def("has_batched_init", [] { return true; });
   m.def("has_fused_chains", [] { return true; });
   m.def("has_box_kernel", [] { return true; });
@@ -104,6 +113,7 @@ PYBIND11_MODULE(_K, m) {
         pybind11::arg("eps"), pybind11::arg("weight_decay"),
         pybind11::arg("step_sizes"),
         pybind11::arg("bias_correction2_sqrts"),
+        pybind11::arg("grad_scale") = pybind11::none(),
         "One-launch AdamW update for a whole list of parameters (kahan "
         "optional per tensor via the compensations list).");
 
@@ -115,6 +125,7 @@ PYBIND11_MODULE(_K, m) {
         pybind11::arg("beta1"), pybind11::arg("beta2"), pybind11::arg("eps"),
         pybind11::arg("weight_decay"), pybind11::arg("step_sizes"),
         pybind11::arg("bias_correction2_sqrts"),
+        pybind11::arg("grad_scale") = pybind11::none(),
         "One-launch AdamW update for a list of parameters whose exp_avg "
         "and/or exp_avg_sq are block-scaled fp8 (float8_e4m3fn or "
         "float8_e5m2 codes plus one fp32 power-of-two scale per 256 "
@@ -126,15 +137,34 @@ PYBIND11_MODULE(_K, m) {
          at::Tensor exp_avg_sq, std::optional<at::Tensor> compensation,
          double lr, double beta1, double beta2, double eps,
          double weight_decay, double step_size,
-         double bias_correction2_sqrt) {
+         double bias_correction2_sqrt,
+         std::optional<at::Tensor> grad_scale) {
         tdx::anyprecision_adamw_step(
             param, grad, exp_avg, exp_avg_sq, std::move(compensation), lr,
             beta1, beta2, eps, weight_decay, step_size,
-            bias_correction2_sqrt);
+            bias_correction2_sqrt, std::move(grad_scale));
       },
       pybind11::arg("param"), pybind11::arg("grad"), pybind11::arg("exp_avg"),
       pybind11::arg("exp_avg_sq"), pybind11::arg("compensation"),
       pybind11::arg("lr"), pybind11::arg("beta1"), pybind11::arg("beta2"),
       pybind11::arg("eps"), pybind11::arg("weight_decay"),
-      pybind11::arg("step_size"), pybind11::arg("bias_correction2_sqrt"));
+      pybind11::arg("step_size"), pybind11::arg("bias_correction2_sqrt"),
+      pybind11::arg("grad_scale") = pybind11::none(),
+      "Fused AdamW update of one parameter. grad_scale (here and in the two "
+      "list forms): optional 1-element float32 tensor on the parameters' "
+      "device; every gradient is multiplied by it in fp32 as it is loaded.");
+
+  m.def(
+      "grad_norm_clip_coef_",
+      [](std::vector<at::Tensor> grads, double max_norm, at::Tensor out) {
+        tdx::grad_norm_clip_coef(std::move(grads), max_norm, out);
+      },
+      pybind11::arg("grads"), pybind11::arg("max_norm"), pybind11::arg("out"),
+      "Global L2 norm of the listed gradients (float32/bf16/fp16, any mix), "
+      "accumulated in fp64, into out[0], and the clip_grad_norm_ coefficient "
+      "min(max_norm / (norm + 1e-6), 1) into out[1]; out is a 2-element "
+      "float32 tensor on the gradients' device. Nothing returns to the host.");
+  m.def("grad_norm_grid_cap", &tdx::grad_norm_grid_cap,
+        "Largest grid of the gradient sum-of-squares kernel; more virtual "
+        "blocks than this are covered by its grid-stride loop.");
 }

@@ -14,6 +14,8 @@
 # (torchdistx_amd._K.anyprecision_adamw_) is used on ROCm GPUs when available
 # instead of the ~10 separate elementwise kernels the eager path launches.
 
+import numbers
+
 import torch
 from torch.optim.optimizer import Optimizer
 
@@ -94,6 +96,39 @@ def _q8_kernel_loaded() -> bool:
         return False
 
 
+def _grad_norm_kernel_loaded() -> bool:
+    try:
+        from torchdistx_amd import _kernels
+
+        return _kernels.has_grad_norm()
+    except Exception:
+        return False
+
+
+_GRAD_NORM_DTYPES = (torch.float32, torch.bfloat16, torch.float16)
+
+
+def _fused_grad_norm_refusal(grads):
+    """Why the fused norm kernel (csrc/hip/grad_norm.hip) cannot take this
+    gradient list, or None if it can."""
+    if not _grad_norm_kernel_loaded():
+        return ("the kernel extension torchdistx_amd._K (with "
+                "grad_norm_clip_coef_) is not loaded")
+    for g in grads:
+        if g.device.type != "cuda":
+            return f"a gradient is on {g.device.type}, not on a GPU"
+        if g.device != grads[0].device:
+            return "the gradients are on more than one GPU"
+        if (g.layout != torch.strided or torch.utils._python_dispatch
+                .is_traceable_wrapper_subclass(g)):
+            return "a gradient is not a plain dense tensor"
+        if g.dtype not in _GRAD_NORM_DTYPES:
+            return f"a gradient is {g.dtype}, not float32/bfloat16/float16"
+        if not g.is_contiguous():
+            return "a gradient is non-contiguous"
+    return None
+
+
 def _is_dtensor(t) -> bool:
     try:
         from torch.distributed.tensor import DTensor
@@ -147,6 +182,17 @@ class AnyPrecisionAdamW(Optimizer):
             step computes in fp32 and rounds once per state store, so it
             is close to but not bitwise-identical with the eager op
             sequence.
+        max_grad_norm: clip the global L2 norm of all gradients (every
+            param group, as ``clip_grad_norm_`` over ``model.parameters()``)
+            to this value inside ``step`` (default: None, no clipping). On
+            the fused path a HIP kernel accumulates the norm in fp64 and
+            leaves the clip coefficient on the device, and the step kernels
+            scale each gradient by it as they load it. ``p.grad`` is never
+            modified — the one deliberate difference from calling
+            ``torch.nn.utils.clip_grad_norm_`` before ``step``. After a
+            step, ``grad_norm`` and ``grad_clip_coef`` hold the norm and the
+            coefficient as 0-dim fp32 device tensors (no host
+            synchronisation). DTensor parameters are not supported yet.
     """
 
     def __init__(
@@ -161,7 +207,15 @@ class AnyPrecisionAdamW(Optimizer):
         variance_dtype=torch.bfloat16,
         compensation_buffer_dtype=torch.bfloat16,
         use_fused=None,
+        max_grad_norm=None,
     ):
+        if max_grad_norm is not None and (
+                isinstance(max_grad_norm, bool)
+                or not isinstance(max_grad_norm, numbers.Real)
+                or not max_grad_norm > 0):
+            raise ValueError(
+                f"max_grad_norm={max_grad_norm!r} is not a positive number"
+            )
         defaults = dict(
             lr=lr,
             betas=betas,
@@ -194,6 +248,11 @@ class AnyPrecisionAdamW(Optimizer):
         # CDNA4 kernel (lets tests and benchmarks assert the fast path
         # actually ran).
         self._fused_steps = 0
+        # Optimizer-wide, not per group: the norm spans all param groups.
+        self.max_grad_norm = max_grad_norm
+        # Views of the [norm, coef] tensor of the last step.
+        self.grad_norm = None
+        self.grad_clip_coef = None
 
     def load_state_dict(self, state_dict):
         """Base-class restore, then re-cast the optimizer states to their
@@ -261,12 +320,69 @@ class AnyPrecisionAdamW(Optimizer):
                 f"AnyPrecisionAdamW step, but {reason}"
             )
 
+    def _clip_norm_and_coef(self):
+        """The 2-element fp32 tensor [norm, coef] of this step's gradients:
+        their global L2 norm and the coefficient of ``clip_grad_norm_``,
+        ``min(max_grad_norm / (norm + 1e-6), 1)``. Stays on the device."""
+        grads = []
+        for group in self.param_groups:
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if _is_dtensor(p) or _is_dtensor(p.grad):
+                    raise RuntimeError(
+                        "max_grad_norm is not supported for DTensor "
+                        "parameters or gradients yet: the local sum of "
+                        "squares would need a reduction across the mesh"
+                    )
+                if p.grad.is_sparse:
+                    raise RuntimeError(
+                        "AnyPrecisionAdamW does not support sparse gradients"
+                    )
+                grads.append(_local_view(p.grad))
+        if not grads:
+            return torch.tensor([0.0, 1.0])
+        refusal = (
+            "use_fused=False forbids it" if self.use_fused is False
+            else _fused_grad_norm_refusal(grads)
+        )
+        if refusal is None:
+            from torchdistx_amd import _kernels
+
+            out = torch.empty(2, dtype=torch.float32, device=grads[0].device)
+            _kernels.grad_norm_clip_coef_(grads, self.max_grad_norm, out)
+            return out
+        if self.use_fused is True:
+            raise RuntimeError(
+                "use_fused=True, but the fused gradient norm for "
+                f"max_grad_norm cannot run: {refusal}. Pass use_fused=None "
+                "to fall back to torch.nn.utils.get_total_norm "
+                "automatically."
+            )
+        # As torch.nn.utils.clip_grad_norm_ forms them.
+        total = torch.nn.utils.get_total_norm(grads, 2.0)
+        coef = torch.clamp(self.max_grad_norm / (total + 1e-6), max=1.0)
+        return torch.stack([total, coef]).to(torch.float32)
+
     @torch.no_grad()
     def step(self, closure=None):
         """Performs a single optimization step."""
         if closure is not None:
             with torch.enable_grad():
                 closure()
+
+        clip = None  # the coefficient as a 1-element tensor, per device
+        if self.max_grad_norm is not None:
+            norm_coef = self._clip_norm_and_coef()
+            self.grad_norm, self.grad_clip_coef = norm_coef[0], norm_coef[1]
+            clip = {norm_coef.device: norm_coef[1:2]}
+
+        def clip_on(device):
+            if clip is None:
+                return None
+            if device not in clip:
+                clip[device] = self.grad_clip_coef.reshape(1).to(device)
+            return clip[device]
 
         for group in self.param_groups:
             beta1, beta2 = group["betas"]
@@ -399,6 +515,7 @@ class AnyPrecisionAdamW(Optimizer):
                             weight_decay,
                             step_size,
                             bias_correction2_sqrt,
+                            clip_on(p_l.device),
                         )
                     else:
                         batch["p"].append(p_l)
@@ -409,6 +526,10 @@ class AnyPrecisionAdamW(Optimizer):
                         batch["step_size"].append(step_size)
                         batch["bc2"].append(bias_correction2_sqrt)
                     continue
+
+                if clip is not None:
+                    # A temporary: p.grad keeps its values.
+                    grad = grad.mul(clip_on(grad.device)[0])
 
                 # Decoupled weight decay (AdamW).
                 if weight_decay:
@@ -460,6 +581,7 @@ class AnyPrecisionAdamW(Optimizer):
                     weight_decay,
                     batch["step_size"],
                     batch["bc2"],
+                    clip_on(batch["p"][0].device),
                 )
             elif batch["p"]:
                 from torchdistx_amd import _kernels
@@ -477,4 +599,5 @@ class AnyPrecisionAdamW(Optimizer):
                     weight_decay,
                     batch["step_size"],
                     batch["bc2"],
+                    clip_on(batch["p"][0].device),
                 )
