@@ -2,9 +2,11 @@
 CDNA4 kernel, on the flagship dtype layout (bf16 params/grad/variance/comp,
 fp32 momentum, Kahan on).
 
-Modes (arguments; default both): "step" is the A/Bs of the step kernels,
-"clip" compares clip_grad_norm_ followed by the fused step with the fused
-max_grad_norm step and times the gradient norm kernels alone."""
+Modes (arguments; default "step" and "clip"): "step" is the A/Bs of the
+step kernels, "clip" compares clip_grad_norm_ followed by the fused step
+with the fused max_grad_norm step and times the gradient norm kernels alone,
+"sr" is the layout table alone (the stochastic-rounding rows next to the
+layouts they are compared with), every row measured twice."""
 import sys, os; sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import time
 
@@ -14,7 +16,7 @@ from torchdistx_amd.optimizers import AnyPrecisionAdamW
 
 assert torch.cuda.is_available()
 MODES = sys.argv[1:] or ["step", "clip"]
-assert set(MODES) <= {"step", "clip"}, MODES
+assert set(MODES) <= {"step", "clip", "sr"}, MODES
 n = 1 << 28  # 268M params (~0.5 GB bf16)
 
 
@@ -92,13 +94,18 @@ for name, batched in ((("per-tensor fused", False), ("batched", True))
 E4M3, E5M2 = torch.float8_e4m3fn, torch.float8_e5m2
 SCALES = 8.0 / 256  # two fp32 scales read and written per 256 elements
 CONFIGS = {
-    # name: (momentum, variance, kahan, bytes per element)
+    # name: (momentum, variance, kahan, bytes per element[, stochastic
+    # rounding of the bf16 parameter])
     "flagship fused (f32 m, bf16 v, kahan)": (
         torch.float32, torch.bfloat16, True, 22.0),
     "flagship fused (f32 m, bf16 v, no kahan)": (
         torch.float32, torch.bfloat16, False, 18.0),
     "q8 (e4m3 m, e5m2 v, no kahan)": (E4M3, E5M2, False, 10.0 + SCALES),
     "q8 (e4m3 m, e5m2 v, kahan)": (E4M3, E5M2, True, 14.0 + SCALES),
+    # Stochastic rounding: no compensation buffer; any state layout takes
+    # the multi-tensor kernel of anyprecision_adamw_q8.hip.
+    "sr (f32 m, bf16 v)": (torch.float32, torch.bfloat16, False, 18.0, True),
+    "sr q8 (e4m3 m, e5m2 v)": (E4M3, E5M2, False, 10.0 + SCALES, True),
 }
 
 
@@ -118,7 +125,7 @@ def timed(opt, steps, repeats):
 
 
 def bench_layout(sizes, config, steps=10, repeats=5):
-    m_dt, v_dt, kahan, _ = config
+    m_dt, v_dt, kahan, _, *sr = config
     torch.manual_seed(2)
     params = [
         torch.nn.Parameter(
@@ -129,6 +136,8 @@ def bench_layout(sizes, config, steps=10, repeats=5):
         params, lr=1e-3, weight_decay=0.01, use_kahan_summation=kahan,
         momentum_dtype=m_dt, variance_dtype=v_dt,
         compensation_buffer_dtype=torch.bfloat16, use_fused=True,
+        **(dict(stochastic_rounding=True, stochastic_rounding_seed=4)
+           if sr else {}),
     )
     for p in params:
         p.grad = torch.randn_like(p)
@@ -139,10 +148,11 @@ def bench_layout(sizes, config, steps=10, repeats=5):
 
 SHAPES = (("2^28 elements", [n]), ("512x16k", [16384] * 512))
 
-for label, sizes in SHAPES * ("step" in MODES):
+for label, sizes in SHAPES * ("step" in MODES or "sr" in MODES):
     # The flagship layouts twice: the second pass is their run-to-run
     # spread under the same conditions.
-    for name in list(CONFIGS) + list(CONFIGS)[:2]:
+    for name in (list(CONFIGS) + list(CONFIGS)[:2] if "step" in MODES
+                 else list(CONFIGS) * 2):
         med, lo, hi = bench_layout(sizes, CONFIGS[name])
         tb = CONFIGS[name][3] * sum(sizes) / (med * 1e-3) / 1e12
         print(f"{label}, {name}: median {med:8.3f} ms/step "

@@ -60,6 +60,9 @@ def anyprecision_adamw_q8_(
     step_sizes: List[float],
     bias_correction2_sqrts: List[float],
     grad_scale: Optional[torch.Tensor] = None,
+    sr_seed: Optional[int] = None,
+    ordinals: Optional[List[int]] = None,
+    steps: Optional[List[int]] = None,
 ) -> None: ...
 def grad_norm_clip_coef_(
     grads: List[torch.Tensor],

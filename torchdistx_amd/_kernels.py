@@ -118,11 +118,16 @@ def anyprecision_adamw_q8_(
     step_sizes,
     bias_correction2_sqrts,
     grad_scale=None,
+    sr_seed=None,
+    ordinals=None,
+    steps=None,
 ):
     """One kernel launch updating every listed parameter whose exp_avg
     and/or exp_avg_sq are block-scaled fp8 (see
     csrc/hip/anyprecision_adamw_q8.hip; a scale entry is None for a state
-    that is not fp8)."""
+    that is not fp8). With sr_seed (an int in [0, 2**63)), bf16 parameters
+    are stored with stochastic rounding; ordinals and steps then give each
+    tensor's index over all param groups and its integer step count."""
     _K.anyprecision_adamw_q8_(
         params,
         [g.contiguous() for g in grads],
@@ -139,6 +144,9 @@ def anyprecision_adamw_q8_(
         step_sizes,
         bias_correction2_sqrts,
         grad_scale,
+        sr_seed,
+        ordinals,
+        steps,
     )
 
 

@@ -23,8 +23,12 @@ struct U4 {
   uint32_t x, y, z, w;
 };
 
+// TDX_PHILOX_NO_HIP_WRAPPERS: for device code compiled with target features
+// other than the HIP headers' (anyprecision_adamw_q8.hip), into which a
+// header wrapper such as __umulhi cannot inline; the plain expression
+// selects the same v_mul_hi_u32.
 TDX_HD uint32_t mulhi32(uint32_t a, uint32_t b) {
-#if defined(__HIP_DEVICE_COMPILE__)
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(TDX_PHILOX_NO_HIP_WRAPPERS)
   return __umulhi(a, b);
 #else
   return static_cast<uint32_t>(

@@ -59,6 +59,26 @@ __device__ __forceinline__ uint32_t asBits(float v) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
+// The bf16 code of the fp32 value v under stochastic rounding with the 16
+// random bits rand16, in integers on the sign-magnitude encoding: the carry
+// of low16(bits) + rand16 moves the kept half one code away from zero, with
+// probability low16(bits) / 65536 exactly, so a representable value never
+// moves. inf and NaN convert as the plain store does; a finite value never
+// becomes an infinity (it stays at the largest finite bf16).
+__device__ __forceinline__ uint32_t bf16BitsStochastic(float v,
+                                                       uint32_t rand16) {
+  const uint32_t b = asBits(roundBarrier(v));
+  if ((b & 0x7f800000u) == 0x7f800000u) {
+    return static_cast<uint32_t>(
+        __builtin_bit_cast(uint16_t, static_cast<__bf16>(asFloat(b))));
+  }
+  const uint32_t b2 = b + rand16;
+  if ((b2 & 0x7f800000u) == 0x7f800000u) {
+    return ((b >> 16) & 0x8000u) | 0x7f7fu;
+  }
+  return b2 >> 16;
+}
+
 // tag: a DT as int (the q8 kernel continues the numbering with its fp8
 // formats, which never reach these two).
 __device__ __forceinline__ float loadOne(const void* p, int tag, int64_t i) {

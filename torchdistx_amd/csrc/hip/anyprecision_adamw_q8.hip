@@ -22,6 +22,13 @@
 // prefix-sum table of virtual blocks as adamw_batched_kernel, a big tensor
 // being a table of one. The dtype of every operand is a per-tensor
 // (workgroup-uniform) switch, as in the batched kernel.
+//
+// Stochastic rounding (kStochastic; docs/anyprecision_adamw.md, "Stochastic
+// rounding"): a bf16 parameter is stored with 16 random bits added below the
+// kept half of its fp32 result. One Philox4x32-10 call per lane and virtual
+// block is exactly the 8 x 16 bits of the lane's eight elements; its counter
+// is (step, tensor ordinal, element index / 8), so the bits are a function of
+// the element alone and not of the grid, the access path or the launch.
 
 #include <hip/hip_runtime.h>
 
@@ -44,6 +51,8 @@
 #endif
 
 #include "adamw_device.h"
+#define TDX_PHILOX_NO_HIP_WRAPPERS
+#include "../core/philox.h"
 
 namespace tdx {
 
@@ -181,6 +190,33 @@ __device__ __forceinline__ void store8Plain(void* p, int tag, int64_t e0,
   }
   *reinterpret_cast<u32x4*>(static_cast<uint16_t*>(p) + e0) =
       u32x4{w[0], w[1], w[2], w[3]};
+}
+
+// Eight bf16 parameters stored with stochastic rounding. Element j of the
+// lane takes 16 bits of r: word j >> 1 of {x, y, z, w}, low half for an even
+// j, high half for an odd one.
+__device__ __forceinline__ void store8Bf16Stochastic(void* p, int64_t e0,
+                                                     int count, bool wide,
+                                                     const float* in,
+                                                     const philox::U4& r) {
+  const uint32_t rw[4] = {r.x, r.y, r.z, r.w};
+  uint32_t w[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    w[k] = bf16BitsStochastic(in[2 * k], rw[k] & 0xffffu) |
+           (bf16BitsStochastic(in[2 * k + 1], rw[k] >> 16) << 16);
+  }
+  uint16_t* q = static_cast<uint16_t*>(p) + e0;
+  if (wide) {
+    *reinterpret_cast<u32x4*>(q) = u32x4{w[0], w[1], w[2], w[3]};
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if (j < count) {
+      q[j] = static_cast<uint16_t>(w[j >> 1] >> (16 * (j & 1)));
+    }
+  }
 }
 
 // The scale of a quant block from the bits of its absmax (sign cleared):
@@ -365,6 +401,10 @@ struct Q8TensorMeta {
   int32_t dt_param, dt_grad, dt_m, dt_v, dt_c;
   float step_size;
   float bias_correction2_sqrt;
+  // Stochastic rounding only: the tensor's index over all param groups and
+  // its step count, the Philox subsequence (step << 32) | ordinal.
+  uint32_t ordinal;
+  uint32_t step;
 };
 
 struct Q8Header {
@@ -373,6 +413,7 @@ struct Q8Header {
   float beta2, eps, weight_decay;
   float one_minus_beta1, one_minus_beta2, decay;  // host-narrowed
   const float* grad_scale;  // nullptr, or one fp32 every gradient is scaled by
+  uint64_t sr_seed;         // Philox key of the stochastic rounding
 };
 
 __device__ __forceinline__ bool alignedTo(const void* p, uintptr_t bytes) {
@@ -380,7 +421,9 @@ __device__ __forceinline__ bool alignedTo(const void* p, uintptr_t bytes) {
 }
 
 // blob layout: int64 prefix[n_tensors] then Q8TensorMeta[n_tensors].
-template <bool kScaled>  // == (h.grad_scale != nullptr)
+// kScaled == (h.grad_scale != nullptr); kStochastic: bf16 parameters store
+// with stochastic rounding (no tensor of the launch has a compensation).
+template <bool kScaled, bool kStochastic>
 __global__ __launch_bounds__(kQ8Threads) void adamw_q8_kernel(
     const uint8_t* __restrict__ blob, Q8Header h) {
   const int64_t* prefix = reinterpret_cast<const int64_t*>(blob);
@@ -473,7 +516,20 @@ __global__ __launch_bounds__(kQ8Threads) void adamw_q8_kernel(
       }
     }
 
-    store8Plain(mt.param, mt.dt_param, e0, count, wide_p, p);
+    bool stored = false;
+    if constexpr (kStochastic) {
+      // Workgroup-uniform: fp32 parameters make no Philox call.
+      if (mt.dt_param == static_cast<int>(DT::kBF16)) {
+        const philox::U4 r = philox::philox10(
+            h.sr_seed, (static_cast<uint64_t>(mt.step) << 32) | mt.ordinal,
+            static_cast<uint64_t>(e0 >> 3));
+        store8Bf16Stochastic(mt.param, e0, count, wide_p, p, r);
+        stored = true;
+      }
+    }
+    if (!stored) {
+      store8Plain(mt.param, mt.dt_param, e0, count, wide_p, p);
+    }
     if (kahan) {
       store8Plain(mt.compensation, mt.dt_c, e0, count, wide_c, c);
     }
@@ -551,7 +607,10 @@ void anyprecision_adamw_q8_step(
     double weight_decay,
     std::vector<double> step_sizes,
     std::vector<double> bias_correction2_sqrts,
-    std::optional<at::Tensor> grad_scale) {
+    std::optional<at::Tensor> grad_scale,
+    std::optional<int64_t> sr_seed,
+    std::optional<std::vector<int64_t>> ordinals,
+    std::optional<std::vector<int64_t>> steps) {
   const size_t n_tensors = params.size();
   TORCH_CHECK(n_tensors > 0, "q8 AdamW: empty tensor list");
   TORCH_CHECK(grads.size() == n_tensors && exp_avgs.size() == n_tensors &&
@@ -562,6 +621,17 @@ void anyprecision_adamw_q8_step(
                   step_sizes.size() == n_tensors &&
                   bias_correction2_sqrts.size() == n_tensors,
               "q8 AdamW: list length mismatch");
+  // Stochastic rounding of the bf16 parameters: the Philox key, and per
+  // tensor the ordinal and the step that form its subsequence.
+  const bool stochastic = sr_seed.has_value();
+  TORCH_CHECK(ordinals.has_value() == stochastic &&
+                  steps.has_value() == stochastic,
+              "q8 AdamW: sr_seed, ordinals and steps go together");
+  if (stochastic) {
+    TORCH_CHECK(*sr_seed >= 0, "q8 AdamW: sr_seed must not be negative");
+    TORCH_CHECK(ordinals->size() == n_tensors && steps->size() == n_tensors,
+                "q8 AdamW: ordinals/steps list length mismatch");
+  }
 
   const size_t prefix_bytes = sizeof(int64_t) * n_tensors;
   const size_t blob_bytes = prefix_bytes + sizeof(Q8TensorMeta) * n_tensors;
@@ -628,6 +698,22 @@ void anyprecision_adamw_q8_step(
         scales[0] != nullptr ? scales[0]->data_ptr<float>() : nullptr;
     mt.exp_avg_sq_scale =
         scales[1] != nullptr ? scales[1]->data_ptr<float>() : nullptr;
+    mt.ordinal = 0;
+    mt.step = 0;
+    if (stochastic) {
+      TORCH_CHECK(!compensations[t].has_value(),
+                  "q8 AdamW: stochastic rounding and Kahan summation "
+                  "exclude each other");
+      TORCH_CHECK(mt.dt_param != static_cast<int>(DT::kF16),
+                  "q8 AdamW: stochastic rounding stores bf16 parameters "
+                  "(fp32 ones as they are); fp16 is not supported");
+      constexpr int64_t k32 = int64_t{1} << 32;
+      TORCH_CHECK((*ordinals)[t] >= 0 && (*ordinals)[t] < k32 &&
+                      (*steps)[t] >= 0 && (*steps)[t] < k32,
+                  "q8 AdamW: ordinals and steps must fit in 32 bits");
+      mt.ordinal = static_cast<uint32_t>((*ordinals)[t]);
+      mt.step = static_cast<uint32_t>((*steps)[t]);
+    }
     mt.step_size = static_cast<float>(step_sizes[t]);
     mt.bias_correction2_sqrt = static_cast<float>(bias_correction2_sqrts[t]);
     prefix_host[t] = total_vblocks;
@@ -659,13 +745,17 @@ void anyprecision_adamw_q8_step(
   h.one_minus_beta2 = static_cast<float>(1.0 - beta2);
   h.decay = static_cast<float>(1.0 - lr * weight_decay);
   h.grad_scale = gradScalePtr(grad_scale, params[0]);
+  h.sr_seed = stochastic ? static_cast<uint64_t>(*sr_seed) : 0;
 
   const int grid =
       static_cast<int>(std::min<int64_t>(total_vblocks, 16384));
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(h.grad_scale != nullptr ? adamw_q8_kernel<true>
-                                             : adamw_q8_kernel<false>,
-                     dim3(grid), dim3(kQ8Threads), 0, stream.stream(),
+  const bool scaled = h.grad_scale != nullptr;
+  auto* kernel = stochastic ? (scaled ? adamw_q8_kernel<true, true>
+                                      : adamw_q8_kernel<false, true>)
+                            : (scaled ? adamw_q8_kernel<true, false>
+                                      : adamw_q8_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kQ8Threads), 0, stream.stream(),
                      static_cast<const uint8_t*>(dev_blob.const_data_ptr()),
                      h);
   C10_HIP_KERNEL_LAUNCH_CHECK();

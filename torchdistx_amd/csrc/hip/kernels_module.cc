@@ -63,7 +63,10 @@ void anyprecision_adamw_q8_step(
     double weight_decay,
     std::vector<double> step_sizes,
     std::vector<double> bias_correction2_sqrts,
-    std::optional<at::Tensor> grad_scale);
+    std::optional<at::Tensor> grad_scale,
+    std::optional<int64_t> sr_seed,
+    std::optional<std::vector<int64_t>> ordinals,
+    std::optional<std::vector<int64_t>> steps);
 
 void grad_norm_clip_coef(std::vector<at::Tensor> grads, double max_norm,
                          at::Tensor& out);
@@ -126,10 +129,16 @@ PYBIND11_MODULE(_K, m) {
         pybind11::arg("weight_decay"), pybind11::arg("step_sizes"),
         pybind11::arg("bias_correction2_sqrts"),
         pybind11::arg("grad_scale") = pybind11::none(),
+        pybind11::arg("sr_seed") = pybind11::none(),
+        pybind11::arg("ordinals") = pybind11::none(),
+        pybind11::arg("steps") = pybind11::none(),
         "One-launch AdamW update for a list of parameters whose exp_avg "
         "and/or exp_avg_sq are block-scaled fp8 (float8_e4m3fn or "
         "float8_e5m2 codes plus one fp32 power-of-two scale per 256 "
-        "elements; the scale entry is None for a state that is not fp8).");
+        "elements; the scale entry is None for a state that is not fp8). "
+        "With sr_seed, bf16 parameters are stored with stochastic rounding: "
+        "Philox4x32-10 keyed by sr_seed, per tensor the subsequence "
+        "(steps[t] << 32) | ordinals[t].");
 
   m.def(
       "anyprecision_adamw_",

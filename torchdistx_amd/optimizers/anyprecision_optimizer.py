@@ -71,6 +71,24 @@ def _check_state_dtypes(momentum_dtype, variance_dtype, compensation_dtype):
         )
 
 
+def _check_stochastic_rounding(group):
+    seed = group["stochastic_rounding_seed"]
+    if seed is not None and (isinstance(seed, bool)
+                             or not isinstance(seed, numbers.Integral)
+                             or not 0 <= seed < 2**63):
+        raise ValueError(
+            f"stochastic_rounding_seed={seed!r} is not an integer in "
+            "[0, 2**63)"
+        )
+    if group["stochastic_rounding"] and group["use_kahan_summation"]:
+        raise ValueError(
+            "stochastic_rounding=True and use_kahan_summation=True exclude "
+            "each other: they are two answers to the same question (keeping "
+            "updates below half a bf16 ulp), and stochastic rounding keeps "
+            "no compensation buffer"
+        )
+
+
 def _q8_scale(state_tensor):
     """Fresh scales for a zero-initialized fp8 state: 1.0 per quant block."""
     n_blocks = -(-state_tensor.numel() // _Q8_BLOCK)
@@ -193,6 +211,23 @@ class AnyPrecisionAdamW(Optimizer):
             step, ``grad_norm`` and ``grad_clip_coef`` hold the norm and the
             coefficient as 0-dim fp32 device tensors (no host
             synchronisation). DTensor parameters are not supported yet.
+        stochastic_rounding: store bf16 parameters with stochastic
+            rounding (default: False): the stored value is unbiased, so
+            updates far below half a bf16 ulp accumulate in expectation,
+            with no compensation buffer. fp32 parameters of the group are
+            stored as always; an fp16 parameter raises ``ValueError``.
+            Excludes ``use_kahan_summation``. Like the fp8 states it
+            exists on the fused GPU path only — ``step`` raises
+            ``RuntimeError`` where that path cannot run.
+        stochastic_rounding_seed: integer in ``[0, 2**63)`` keying the
+            random bits, which are a function of (seed, step, index of the
+            parameter over all groups, element index) alone. None (default)
+            draws one from torch's default CPU generator at construction,
+            so ``torch.manual_seed`` decides it; without stochastic
+            rounding nothing is drawn. Data-parallel replicas need the
+            same seed on every rank — pass it explicitly or seed the ranks
+            identically — and then stay bitwise in sync. The seed is part
+            of ``state_dict()["param_groups"]``.
     """
 
     def __init__(
@@ -208,6 +243,8 @@ class AnyPrecisionAdamW(Optimizer):
         compensation_buffer_dtype=torch.bfloat16,
         use_fused=None,
         max_grad_norm=None,
+        stochastic_rounding=False,
+        stochastic_rounding_seed=None,
     ):
         if max_grad_norm is not None and (
                 isinstance(max_grad_norm, bool)
@@ -225,10 +262,13 @@ class AnyPrecisionAdamW(Optimizer):
             momentum_dtype=momentum_dtype,
             variance_dtype=variance_dtype,
             compensation_buffer_dtype=compensation_buffer_dtype,
+            stochastic_rounding=stochastic_rounding,
+            stochastic_rounding_seed=stochastic_rounding_seed,
         )
         _check_state_dtypes(
             momentum_dtype, variance_dtype, compensation_buffer_dtype
         )
+        _check_stochastic_rounding(defaults)
         super().__init__(params, defaults)
         for group in self.param_groups:
             _check_state_dtypes(
@@ -236,6 +276,7 @@ class AnyPrecisionAdamW(Optimizer):
                 group["variance_dtype"],
                 group["compensation_buffer_dtype"],
             )
+            _check_stochastic_rounding(group)
             for p in group["params"]:
                 if p.dtype in _FP8_DTYPES:
                     raise ValueError(
@@ -243,6 +284,15 @@ class AnyPrecisionAdamW(Optimizer):
                         "is for the optimizer states exp_avg and "
                         "exp_avg_sq only"
                     )
+        unseeded = [g for g in self.param_groups
+                    if g["stochastic_rounding_seed"] is None]
+        if unseeded and any(g["stochastic_rounding"]
+                            for g in self.param_groups):
+            # One draw from the default CPU generator, and only when
+            # stochastic rounding is on.
+            seed = int(torch.randint(0, 2**63 - 1, (1,)).item())
+            for group in unseeded:
+                group["stochastic_rounding_seed"] = seed
         self.use_fused = use_fused
         # Diagnostic: number of parameter updates that took the fused
         # CDNA4 kernel (lets tests and benchmarks assert the fast path
@@ -294,16 +344,20 @@ class AnyPrecisionAdamW(Optimizer):
                     state[k] = saved[k].detach().to(
                         device=state[k].device, dtype=dtype, copy=True)
 
-    def _check_q8_can_run(self, p, kernel_loaded):
+    def _check_q8_can_run(self, p, kernel_loaded, sr=False):
         """fp8 states exist on the fused path only (torch has no fp8
         ``lerp_``/``addcmul_``, and an eager emulation would be a second
-        definition of the format): name why it cannot run."""
+        definition of the format), and so does stochastic rounding (``sr``;
+        its random bits are defined by the kernel): name why it cannot
+        run."""
         reason = None
         if self.use_fused is False:
             reason = "use_fused=False forbids the fused step"
         elif _is_dtensor(p):
-            reason = ("the parameter is a DTensor, and a per-local-shard "
-                      "scale tensor has no DTensor placement yet")
+            reason = ("the parameter is a DTensor, " + (
+                "which stochastic rounding does not cover yet" if sr else
+                "and a per-local-shard scale tensor has no DTensor "
+                "placement yet"))
         elif p.device.type != "cuda":
             reason = f"the parameter is on {p.device.type}, not on a GPU"
         elif not kernel_loaded:
@@ -314,10 +368,12 @@ class AnyPrecisionAdamW(Optimizer):
         elif not p.is_contiguous():
             reason = "the parameter is non-contiguous"
         if reason is not None:
+            what = ("stochastic rounding (stochastic_rounding=True) needs"
+                    if sr else
+                    "fp8 optimizer states (momentum_dtype/variance_dtype = "
+                    "float8_e4m3fn/float8_e5m2) need")
             raise RuntimeError(
-                "fp8 optimizer states (momentum_dtype/variance_dtype = "
-                "float8_e4m3fn/float8_e5m2) need the fused "
-                f"AnyPrecisionAdamW step, but {reason}"
+                f"{what} the fused AnyPrecisionAdamW step, but {reason}"
             )
 
     def _clip_norm_and_coef(self):
@@ -384,6 +440,7 @@ class AnyPrecisionAdamW(Optimizer):
                 clip[device] = self.grad_clip_coef.reshape(1).to(device)
             return clip[device]
 
+        ordinal = -1  # of a parameter over all groups, as state_dict counts
         for group in self.param_groups:
             beta1, beta2 = group["betas"]
             lr = group["lr"]
@@ -400,14 +457,21 @@ class AnyPrecisionAdamW(Optimizer):
             # launch overhead would otherwise dominate the small ones.
             batch = {k: [] for k in
                      ("p", "g", "m", "v", "c", "step_size", "bc2")}
-            # A group with an fp8 state takes the block-scaled kernel for
-            # every parameter, whatever its size, in one launch.
-            q8 = momentum_dtype in _Q8_DTYPES or variance_dtype in _Q8_DTYPES
+            # A group with an fp8 state, or with stochastic rounding,
+            # takes the block-scaled kernel for every parameter, whatever
+            # its size and state dtypes, in one launch.
+            sr = group.get("stochastic_rounding", False)
+            if sr:
+                _check_stochastic_rounding(group)
+                batch["ordinal"], batch["step"] = [], []
+            q8 = (sr or momentum_dtype in _Q8_DTYPES
+                  or variance_dtype in _Q8_DTYPES)
             if q8:
                 batch["ms"], batch["vs"] = [], []
                 q8_kernel = _q8_kernel_loaded()
 
             for p in group["params"]:
+                ordinal += 1
                 if p.grad is None:
                     continue
                 if p.grad.is_sparse:
@@ -416,7 +480,13 @@ class AnyPrecisionAdamW(Optimizer):
                     )
 
                 if q8:
-                    self._check_q8_can_run(p, q8_kernel)
+                    self._check_q8_can_run(p, q8_kernel, sr)
+                if sr and p.dtype == torch.float16:
+                    raise ValueError(
+                        "stochastic_rounding=True stores bfloat16 "
+                        "parameters (float32 ones as they are); a float16 "
+                        "parameter is not supported"
+                    )
 
                 state = self.state[p]
                 if len(state) == 0:
@@ -470,7 +540,8 @@ class AnyPrecisionAdamW(Optimizer):
                 if q8:
                     if not can_fuse:
                         raise RuntimeError(
-                            "fp8 optimizer states need the fused "
+                            ("stochastic rounding needs" if sr else
+                             "fp8 optimizer states need") + " the fused "
                             "AnyPrecisionAdamW step, which cannot run for "
                             "this parameter: its gradient or states are "
                             "non-contiguous or mismatched in size"
@@ -485,6 +556,9 @@ class AnyPrecisionAdamW(Optimizer):
                     batch["c"].append(c_l)
                     batch["step_size"].append(step_size)
                     batch["bc2"].append(bias_correction2_sqrt)
+                    if sr:
+                        batch["ordinal"].append(ordinal)
+                        batch["step"].append(int(step))
                     continue
                 if self.use_fused is True and not can_fuse:
                     raise RuntimeError(
@@ -582,6 +656,8 @@ class AnyPrecisionAdamW(Optimizer):
                     batch["step_size"],
                     batch["bc2"],
                     clip_on(batch["p"][0].device),
+                    *((group["stochastic_rounding_seed"], batch["ordinal"],
+                       batch["step"]) if sr else ()),
                 )
             elif batch["p"]:
                 from torchdistx_amd import _kernels
