@@ -2,11 +2,16 @@
 // elements-per-thread and grid size on a 4 GiB bf16 buffer.
 // Build/run on the GPU box:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 scripts/rng_tune.hip -o /tmp/rng_tune && /tmp/rng_tune
+// `rng_tune valu` runs the VALU-trim comparison of the normal kernel
+// instead (profiles/normal_fill_valu.md).
 #include <hip/hip_bf16.h>
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
+
+#include "../torchdistx_amd/csrc/core/box_muller.h"
 
 #define CHECK(x)                                            \
   do {                                                      \
@@ -422,6 +427,151 @@ __global__ void normal_bf16_rsplit2(__hip_bfloat16* __restrict__ out,
   }
 }
 
+// ---------------------------------------------------------------------------
+// VALU-trim candidates for the shipped normal kernel (Philox-7 + log2
+// Box-Muller), one flag per step so each is measured alone and all
+// together (`rng_tune valu`, results in profiles/normal_fill_valu.md).
+// Every step is meant to leave the output bits unchanged; the probe
+// checks that with a checksum against the flag-free baseline.
+// ---------------------------------------------------------------------------
+constexpr int kMul64 = 1;  // one 64-bit product per Philox multiply
+constexpr int kXor3 = 2;   // hi ^ c ^ k through the three-input bit-op
+constexpr int kSqrt = 4;   // sqrt refinement without range scaling / class
+constexpr int kFold = 8;   // cvt * 2^-16 * 2pi as one multiply
+
+template <int F>
+__device__ __forceinline__ uint2 mulhilo32_v(uint32_t a, uint32_t b) {
+  if constexpr ((F & kMul64) != 0) {
+    const uint64_t p = static_cast<uint64_t>(a) * b;
+    return make_uint2(static_cast<uint32_t>(p),
+                      static_cast<uint32_t>(p >> 32));
+  } else {
+    return mulhilo32(a, b);
+  }
+}
+
+template <int F>
+__device__ __forceinline__ uint32_t xor3_v(uint32_t a, uint32_t b,
+                                           uint32_t c) {
+  if constexpr ((F & kXor3) != 0) {
+    return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
+  } else {
+    return a ^ b ^ c;
+  }
+}
+
+template <int R, int F>
+__device__ __forceinline__ uint4 philox_v(uint64_t seed, uint64_t subseq,
+                                          uint64_t offset) {
+  constexpr uint32_t kW0 = 0x9E3779B9u, kW1 = 0xBB67AE85u;
+  constexpr uint32_t kM0 = 0xD2511F53u, kM1 = 0xCD9E8D57u;
+  uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+  uint4 c = make_uint4((uint32_t)offset, (uint32_t)(offset >> 32),
+                       (uint32_t)subseq, (uint32_t)(subseq >> 32));
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    uint2 r0 = mulhilo32_v<F>(kM0, c.x);
+    uint2 r1 = mulhilo32_v<F>(kM1, c.z);
+    c = make_uint4(xor3_v<F>(r1.y, c.y, k0), r1.x, xor3_v<F>(r0.y, c.w, k1),
+                   r0.x);
+    k0 += kW0;
+    k1 += kW1;
+  }
+  return c;
+}
+
+// The product's sqrt_box_muller: v_sqrt_f32 plus the shared +-1 ulp
+// fix-up, x and the two residuals pinned in registers so the multiplies
+// and fmas are not paired into packed fp32 instructions.
+__device__ __forceinline__ float pin_vgpr(float v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+__device__ __forceinline__ float sqrt_refined(float x) {
+  x = pin_vgpr(x);
+  return tdx::box_muller::sqrt_fixup(__builtin_amdgcn_sqrtf(x), x,
+                                     [](float v) { return pin_vgpr(v); });
+}
+
+template <int F>
+__global__ void normal_bf16_valu(__hip_bfloat16* __restrict__ out,
+                                 uint32_t n8, float a, float b,
+                                 uint64_t seed, uint64_t offset) {
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < n8;
+       g += stride) {
+    uint4 bits = philox_v<7, F>(seed, g, offset);
+    uint32_t w[4] = {bits.x, bits.y, bits.z, bits.w};
+    V8 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float u1 = fmaxf((float)(w[j] & 0xffffu) * (1.0f / 65536.0f),
+                       1.1754944e-38f);
+      const float x = tdx::box_muller::kNeg2Ln2 * __log2f(u1);
+      float r;
+      if constexpr ((F & kSqrt) != 0) {
+        r = sqrt_refined(x);
+      } else {
+        r = sqrtf(x);
+      }
+      float angle;
+      if constexpr ((F & kFold) != 0) {
+        angle = (float)(w[j] >> 16) * tdx::box_muller::kAngleScale16;
+      } else {
+        angle = 6.2831853071795865f * ((float)(w[j] >> 16) * (1.0f / 65536.0f));
+      }
+      float sn, cs;
+      __sincosf(angle, &sn, &cs);
+      float v0 = fmaf(r * cs, b, a);
+      float v1 = fmaf(r * sn, b, a);
+      // Same rounding pin as from_float() in init_kernels.hip.
+      asm volatile("" : "+v"(v0));
+      asm volatile("" : "+v"(v1));
+      v.v[j * 2 + 0] = __float2bfloat16(v0);
+      v.v[j * 2 + 1] = __float2bfloat16(v1);
+    }
+    *reinterpret_cast<V8*>(out + (uint64_t)g * 8) = v;
+  }
+}
+
+template <int F>
+__global__ void uniform_bf16_valu(__hip_bfloat16* __restrict__ out,
+                                  uint32_t n8, float a, float b,
+                                  uint64_t seed, uint64_t offset) {
+  const uint32_t stride = gridDim.x * blockDim.x;
+  for (uint32_t g = blockIdx.x * blockDim.x + threadIdx.x; g < n8;
+       g += stride) {
+    uint4 bits = philox_v<10, F>(seed, g, offset);
+    uint32_t w[4] = {bits.x, bits.y, bits.z, bits.w};
+    V8 v;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float v0 = fmaf((float)(w[j] & 0xffffu) * (1.0f / 65536.0f), b, a);
+      float v1 = fmaf((float)(w[j] >> 16) * (1.0f / 65536.0f), b, a);
+      asm volatile("" : "+v"(v0));
+      asm volatile("" : "+v"(v1));
+      v.v[j * 2 + 0] = __float2bfloat16(v0);
+      v.v[j * 2 + 1] = __float2bfloat16(v1);
+    }
+    *reinterpret_cast<V8*>(out + (uint64_t)g * 8) = v;
+  }
+}
+
+__global__ void zero_u64(unsigned long long* p) { *p = 0; }
+
+// Order-sensitive 64-bit checksum of the buffer's 32-bit words.
+__global__ void checksum_words(const uint32_t* __restrict__ in, uint64_t n,
+                               unsigned long long* __restrict__ acc) {
+  unsigned long long s = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    s += (unsigned long long)in[i] * (2ull * i + 1ull);
+  }
+  atomicAdd(acc, s);
+}
+
 template <typename K>
 double benchB(K kernel, __hip_bfloat16* buf, uint32_t n8, int blocks,
               int iters, int threads) {
@@ -462,11 +612,103 @@ double bench(K kernel, __hip_bfloat16* buf, uint32_t n8, int blocks,
   return bytes / (ms / 1e3) / 1e12;  // TB/s
 }
 
-int main() {
+using TuneKernel = void (*)(__hip_bfloat16*, uint32_t, float, float, uint64_t,
+                            uint64_t);
+struct Variant {
+  const char* name;
+  TuneKernel kernel;
+  int base;  // index of the variant whose bits this one must reproduce
+};
+
+// `rng_tune valu`: every candidate against the baseline, alternating
+// inside one process at the product's launch shape (16384 x 256).
+int run_valu(__hip_bfloat16* buf, uint32_t n8) {
+  constexpr int kAll = kMul64 | kXor3 | kSqrt | kFold;
+  const Variant variants[] = {
+      {"normal  baseline (r7+log2)", normal_bf16_valu<0>, 0},
+      {"normal  +mul64", normal_bf16_valu<kMul64>, 0},
+      {"normal  +xor3", normal_bf16_valu<kXor3>, 0},
+      {"normal  +sqrt", normal_bf16_valu<kSqrt>, 0},
+      {"normal  +fold", normal_bf16_valu<kFold>, 0},
+      {"normal  +sqrt+fold", normal_bf16_valu<kSqrt | kFold>, 0},
+      {"normal  +sqrt+fold+mul64", normal_bf16_valu<kSqrt | kFold | kMul64>,
+       0},
+      {"normal  +sqrt+fold+xor3", normal_bf16_valu<kSqrt | kFold | kXor3>, 0},
+      {"normal  all four", normal_bf16_valu<kAll>, 0},
+      {"uniform baseline (r10)", uniform_bf16_valu<0>, 9},
+      {"uniform +mul64", uniform_bf16_valu<kMul64>, 9},
+      {"uniform +xor3", uniform_bf16_valu<kXor3>, 9},
+      {"uniform +mul64+xor3", uniform_bf16_valu<kMul64 | kXor3>, 9},
+  };
+  constexpr int kN = sizeof(variants) / sizeof(variants[0]);
+  constexpr int kReps = 9, kIters = 10, kBlocks = 16384;
+
+  unsigned long long* acc;
+  CHECK(hipMalloc(&acc, sizeof(*acc) * kN));
+  unsigned long long sums[kN];
+  for (int i = 0; i < kN; ++i) {
+    zero_u64<<<1, 1>>>(acc + i);
+    // mean 0, std 1: the transform's bits reach the bf16 output unscaled.
+    variants[i].kernel<<<kBlocks, 256>>>(buf, n8, 0.0f, 1.0f, 42, 4);
+    checksum_words<<<4096, 256>>>(reinterpret_cast<const uint32_t*>(buf),
+                                  (uint64_t)n8 * 4, acc + i);
+  }
+  CHECK(hipDeviceSynchronize());
+  CHECK(hipMemcpy(sums, acc, sizeof(sums), hipMemcpyDeviceToHost));
+
+  // Warm the clocks (profiles/dvfs_ramp_note.md) before the first timing.
+  for (int i = 0; i < 200; ++i) {
+    variants[0].kernel<<<kBlocks, 256>>>(buf, n8, 0.25f, 0.02f, 42, 4);
+  }
+  CHECK(hipDeviceSynchronize());
+
+  hipEvent_t e0, e1;
+  CHECK(hipEventCreate(&e0));
+  CHECK(hipEventCreate(&e1));
+  static double tbps[kN][kReps];
+  for (int rep = 0; rep < kReps; ++rep) {
+    for (int i = 0; i < kN; ++i) {
+      CHECK(hipEventRecord(e0));
+      for (int it = 0; it < kIters; ++it) {
+        variants[i].kernel<<<kBlocks, 256>>>(buf, n8, 0.25f, 0.02f, 42, 4);
+      }
+      CHECK(hipEventRecord(e1));
+      CHECK(hipEventSynchronize(e1));
+      float ms;
+      CHECK(hipEventElapsedTime(&ms, e0, e1));
+      tbps[i][rep] = (double)n8 * 16.0 * kIters / (ms / 1e3) / 1e12;
+    }
+  }
+  printf("%-30s %8s %8s %8s  %s\n", "variant", "median", "min", "max",
+         "bits vs baseline");
+  for (int i = 0; i < kN; ++i) {
+    double* t = tbps[i];
+    for (int x = 1; x < kReps; ++x) {
+      for (int y = x; y > 0 && t[y - 1] > t[y]; --y) {
+        double tmp = t[y];
+        t[y] = t[y - 1];
+        t[y - 1] = tmp;
+      }
+    }
+    printf("%-30s %8.3f %8.3f %8.3f  %s (%016llx)\n", variants[i].name,
+           t[kReps / 2], t[0], t[kReps - 1],
+           sums[i] == sums[variants[i].base] ? "same" : "DIFFERENT", sums[i]);
+  }
+  CHECK(hipFree(acc));
+  return 0;
+}
+
+int main(int argc, char** argv) {
   const uint64_t bytes = 4ull << 30;
   const uint32_t n8 = (uint32_t)(bytes / 16);
   __hip_bfloat16* buf;
   CHECK(hipMalloc(&buf, bytes));
+
+  if (argc > 1 && strcmp(argv[1], "valu") == 0) {
+    int rc = run_valu(buf, n8);
+    hipFree(buf);
+    return rc;
+  }
 
   for (int blocks : {4096, 8192, 16384}) {
     printf("blocks=%d\n", blocks);
