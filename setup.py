@@ -56,6 +56,7 @@ hip_sources = [
     os.path.join(CSRC, "hip", "anyprecision_adamw.hip"),
     os.path.join(CSRC, "hip", "anyprecision_adamw_q8.hip"),
     os.path.join(CSRC, "hip", "grad_norm.hip"),
+    os.path.join(CSRC, "hip", "slowmo.hip"),
     os.path.join(CSRC, "hip", "kernels_module.cc"),
 ]
 if all(os.path.exists(s) for s in hip_sources) and torch.version.hip:

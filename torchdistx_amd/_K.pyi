@@ -1,6 +1,6 @@
 # Typing stub for the CDNA4 kernel extension.
 
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -70,6 +70,24 @@ def grad_norm_clip_coef_(
     out: torch.Tensor,
 ) -> None: ...
 def grad_norm_grid_cap() -> int: ...
+def has_slowmo() -> bool: ...
+def slowmo_flat_layout(
+    params: List[torch.Tensor],
+) -> Tuple[List[int], int]: ...
+def slowmo_pack_(
+    params: List[torch.Tensor],
+    flat: torch.Tensor,
+    world_size: int,
+) -> None: ...
+def slowmo_outer_step_(
+    params: List[torch.Tensor],
+    prevs: List[torch.Tensor],
+    momenta: List[torch.Tensor],
+    flat: Optional[torch.Tensor],
+    lrs: List[float],
+    slowmo_factor: float,
+    slowmo_lr: float,
+) -> None: ...
 def batched_init_(
     tensors: List[torch.Tensor],
     dists: List[int],

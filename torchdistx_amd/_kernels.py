@@ -165,3 +165,40 @@ def grad_norm_clip_coef_(grads, max_norm, out):
     tensor on the gradients' device; nothing returns to the host. The step
     wrappers above take out[1:2] as grad_scale."""
     _K.grad_norm_clip_coef_(grads, max_norm, out)
+
+
+def has_slowmo() -> bool:
+    return (
+        _HAS_K
+        and torch.cuda.is_available()
+        and hasattr(_K, "has_slowmo")
+    )
+
+
+def slowmo_flat_layout(params):
+    """(offsets, total_numel), in elements, of the flat buffer the SlowMo
+    kernels use for these parameters: every slot starts at a multiple of 8.
+    Host only."""
+    return _K.slowmo_flat_layout(params)
+
+
+def slowmo_pack_(params, flat, world_size):
+    """One kernel launch writing every listed parameter, divided by
+    world_size, into its slot of flat (see csrc/hip/slowmo.hip,
+    slowmo_pack_kernel): bitwise what cat(params).div_(world_size) holds."""
+    if params:
+        with torch.cuda.device(params[0].device):
+            _K.slowmo_pack_(params, flat, world_size)
+
+
+def slowmo_outer_step_(params, prevs, momenta, flat, lrs, slowmo_factor,
+                       slowmo_lr):
+    """One kernel launch applying the slow-momentum outer step to every
+    listed parameter (see csrc/hip/slowmo.hip, slowmo_outer_step_kernel).
+    flat: the all-reduced buffer slowmo_pack_ filled, or None to take the
+    parameters themselves as the averaged values. lrs: one learning rate
+    per tensor."""
+    if params:
+        with torch.cuda.device(params[0].device):
+            _K.slowmo_outer_step_(params, prevs, momenta, flat, lrs,
+                                  slowmo_factor, slowmo_lr)

@@ -73,6 +73,19 @@ void grad_norm_clip_coef(std::vector<at::Tensor> grads, double max_norm,
 
 int64_t grad_norm_grid_cap();
 
+std::tuple<std::vector<int64_t>, int64_t> slowmo_flat_layout(
+    const std::vector<at::Tensor>& params);
+
+void slowmo_pack(std::vector<at::Tensor> params, at::Tensor& flat,
+                 int64_t world_size);
+
+void slowmo_outer_step(std::vector<at::Tensor> params,
+                       std::vector<at::Tensor> prevs,
+                       std::vector<at::Tensor> momenta,
+                       std::optional<at::Tensor> flat,
+                       std::vector<double> lrs, double slowmo_factor,
+                       double slowmo_lr);
+
 }  // namespace tdx
 
 PYBIND11_MODULE(_K, m) {
@@ -83,6 +96,7 @@ PYBIND11_MODULE(_K, m) {
   m.def("has_anyprecision_adamw_batched", [] { return true; });
   m.def("has_anyprecision_adamw_q8", [] { return true; });
   m.def("has_grad_norm", [] { return true; });
+  m.def("has_slowmo", [] { return true; });
   m.def("has_batched_init", [] { return true; });
   m.def("has_fused_chains", [] { return true; });
   m.def("has_box_kernel", [] { return true; });
@@ -176,4 +190,38 @@ PYBIND11_MODULE(_K, m) {
   m.def("grad_norm_grid_cap", &tdx::grad_norm_grid_cap,
         "Largest grid of the gradient sum-of-squares kernel; more virtual "
         "blocks than this are covered by its grid-stride loop.");
+
+  m.def("slowmo_flat_layout", &tdx::slowmo_flat_layout,
+        pybind11::arg("params"),
+        "Host only: (offsets, total_numel) of the flat buffer the SlowMo "
+        "kernels use for these parameters, in elements; every slot starts "
+        "at a multiple of 8 and total_numel is one too.");
+  m.def(
+      "slowmo_pack_",
+      [](std::vector<at::Tensor> params, at::Tensor flat,
+         int64_t world_size) {
+        tdx::slowmo_pack(std::move(params), flat, world_size);
+      },
+      pybind11::arg("params"), pybind11::arg("flat"),
+      pybind11::arg("world_size"),
+      "One launch writing every listed parameter (float32/bf16/fp16, any "
+      "mix), divided by world_size as ATen divides by a host scalar, into "
+      "its slot of flat (slowmo_flat_layout); the padding is not written.");
+  m.def(
+      "slowmo_outer_step_",
+      [](std::vector<at::Tensor> params, std::vector<at::Tensor> prevs,
+         std::vector<at::Tensor> momenta, std::optional<at::Tensor> flat,
+         std::vector<double> lrs, double slowmo_factor, double slowmo_lr) {
+        tdx::slowmo_outer_step(std::move(params), std::move(prevs),
+                               std::move(momenta), std::move(flat),
+                               std::move(lrs), slowmo_factor, slowmo_lr);
+      },
+      pybind11::arg("params"), pybind11::arg("prevs"),
+      pybind11::arg("momenta"), pybind11::arg("flat"), pybind11::arg("lrs"),
+      pybind11::arg("slowmo_factor"), pybind11::arg("slowmo_lr"),
+      "One-launch slow-momentum outer step for a list of parameters: "
+      "m <- fma(prev - a, 1/lr, factor * m), prev <- p <- prev - slowmo_lr * "
+      "lr * m in fp32, with a the parameter's slot of flat rounded to the "
+      "parameter's dtype, or the parameter itself when flat is None. lrs "
+      "gives each tensor's learning rate.");
 }
