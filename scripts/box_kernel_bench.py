@@ -10,9 +10,8 @@ never materialized.
 
 All variants run in one process, alternating, `--repeats` timed windows
 each (a synchronise on both sides, `--iters` calls inside); medians and
-the min-max spread are reported. TDX_BOX_PLAIN_DIV=1 makes the untailed
-32-bit normal box kernels divide with `/` instead of the multiply-shift
-divisor, so both forms are timed side by side.
+the min-max spread are reported. The window op launches the same kernel
+with one level, so its rows show what the second level costs.
 
 Usage: python scripts/box_kernel_bench.py [--iters 300] [--repeats 5]
 """
@@ -38,30 +37,20 @@ SEED, OFFSET = 1, 4
 
 
 def window_time(fn, iters):
-    if getattr(fn, "plain", False):
-        os.environ["TDX_BOX_PLAIN_DIV"] = "1"
-    try:
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(iters):
-            fn()
-        torch.cuda.synchronize()
-        return (time.perf_counter() - t0) / iters
-    finally:
-        os.environ.pop("TDX_BOX_PLAIN_DIV", None)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / iters
 
 
-def box_call(shard, lo_col, hi_col, plain=False):
+def box_call(shard, lo_col, hi_col):
     rows = R // 2
     args = (shard, [2, rows], [R * C, C], hi_col - lo_col,
             1 * R * C + lo_col, 1, 0.0, 1.0, [], [], [], FULL_NUMEL, SEED,
             OFFSET)
-
-    def call():
-        torch.ops.tdx.rng_box_(*args)
-
-    call.plain = plain  # window_time sets the switch around the window
-    return call
+    return lambda: torch.ops.tdx.rng_box_(*args)
 
 
 def win_call(shard, lo_col, hi_col):
@@ -111,31 +100,17 @@ def main():
     wbf_odd = torch.empty(R, 1023, dtype=torch.bfloat16, device="cuda")
     wf32 = torch.empty(R, 1024, dtype=torch.float32, device="cuda")
 
-    box_call(bf, 1024, 2048)()
-    a = bf.clone()
-    window_time(box_call(bf, 1024, 2048, plain=True), 1)
-    assert torch.equal(a, bf), "plain-division kernel differs"
-    del a
-
     # (name, call, bytes per call, iterations per window)
     n, it, ait = bf.numel(), opts.iters, opts.api_iters
     variants = [
-        ("rng_box_ bf16 aligned (multiply-shift)",
-         box_call(bf, 1024, 2048), n * 2, it),
-        ("rng_box_ bf16 aligned (plain /)",
-         box_call(bf, 1024, 2048, plain=True), n * 2, it),
+        ("rng_box_ bf16 aligned", box_call(bf, 1024, 2048), n * 2, it),
         ("normal_shard_win_ bf16 aligned, same numel",
          win_call(wbf, 1024, 2048), n * 2, it),
         ("rng_box_ bf16 odd width 1025:2048",
          box_call(bf_odd, 1025, 2048), bf_odd.numel() * 2, it),
-        ("rng_box_ bf16 odd width (plain /)",
-         box_call(bf_odd, 1025, 2048, plain=True), bf_odd.numel() * 2, it),
         ("normal_shard_win_ bf16 odd width",
          win_call(wbf_odd, 1025, 2048), wbf_odd.numel() * 2, it),
-        ("rng_box_ f32 aligned (multiply-shift)",
-         box_call(f32, 1024, 2048), n * 4, it),
-        ("rng_box_ f32 aligned (plain /)",
-         box_call(f32, 1024, 2048, plain=True), n * 4, it),
+        ("rng_box_ f32 aligned", box_call(f32, 1024, 2048), n * 4, it),
         ("normal_shard_win_ f32 aligned, same numel",
          win_call(wf32, 1024, 2048), n * 4, it),
         ("materialize_tensor_block (API, allocates)", api_box, n * 2, ait),

@@ -54,12 +54,20 @@ def _k_elems(dtype):
 
 
 def _numels(dtype):
+    # (numel, misaligned). 2405 = 8 * 300 + 5: full groups and a partial
+    # last one, past one 2048-element ATen block; then the same into a
+    # destination that is not 16-byte aligned (stored element by element).
     k = _k_elems(dtype)
-    return [1, k - 1, k, k + 1, 1_000_003]
+    return [(n, False) for n in (1, k - 1, k, k + 1, 2405, 1_000_003)] + [
+        (2405, True)]
 
 
-def _chain(numel, dtype, dist, p0, p1, ops, s0, s1):
-    out = torch.empty(numel, device="cuda", dtype=dtype)
+def _chain(numel, dtype, dist, p0, p1, ops, s0, s1, misaligned=False):
+    if misaligned:  # one element into a larger buffer
+        out = torch.empty(numel + 1, device="cuda", dtype=dtype)[1:]
+        assert out.data_ptr() % 16 != 0 and out.is_contiguous()
+    else:
+        out = torch.empty(numel, device="cuda", dtype=dtype)
     torch.ops.tdx.rng_chain_(out, dist, p0, p1, ops, s0, s1,
                              seed=SEED, offset=OFFSET)
     return out
@@ -67,7 +75,7 @@ def _chain(numel, dtype, dist, p0, p1, ops, s0, s1):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 def test_trunc_normal_chain_bitwise(dtype) -> None:
-    for numel in _numels(dtype):
+    for numel, misaligned in _numels(dtype):
         ref = torch.empty(numel, device="cuda", dtype=dtype)
         torch.ops.tdx.uniform_(ref, -0.9, 0.95, seed=SEED, offset=OFFSET)
         ref.erfinv_().mul_(STD_SQRT2).add_(0.1).clamp_(-1.0, 1.5)
@@ -75,8 +83,9 @@ def test_trunc_normal_chain_bitwise(dtype) -> None:
         assert not ref.isnan().any()
         out = _chain(numel, dtype, 0, -0.9, 0.95,
                      [ERFINV, MUL, ADD, CLAMP],
-                     [0.0, STD_SQRT2, 0.1, -1.0], [0.0, 0.0, 0.0, 1.5])
-        assert torch.equal(out, ref), (dtype, numel)
+                     [0.0, STD_SQRT2, 0.1, -1.0], [0.0, 0.0, 0.0, 1.5],
+                     misaligned)
+        assert torch.equal(out, ref), (dtype, numel, misaligned)
 
 
 def test_f32_erfinv_chain_accuracy() -> None:
@@ -105,15 +114,15 @@ def test_f32_erfinv_chain_accuracy() -> None:
 def test_exact_op_chain_bitwise(dtype) -> None:
     """mul -> add on an f32 tensor is the pair a contracting compiler
     would turn into one FMA."""
-    for numel in _numels(dtype):
+    for numel, misaligned in _numels(dtype):
         ref = torch.empty(numel, device="cuda", dtype=dtype)
         torch.ops.tdx.uniform_(ref, -3.0, 5.0, seed=SEED, offset=OFFSET)
         ref.mul_(1.1).add_(-0.3).neg_().abs_().clamp_min_(0.75)
         assert not ref.isnan().any()
         out = _chain(numel, dtype, 0, -3.0, 5.0,
                      [MUL, ADD, NEG, ABS, CLAMP_MIN],
-                     [1.1, -0.3, 0.0, 0.0, 0.75], [0.0] * 5)
-        assert torch.equal(out, ref), (dtype, numel)
+                     [1.1, -0.3, 0.0, 0.0, 0.75], [0.0] * 5, misaligned)
+        assert torch.equal(out, ref), (dtype, numel, misaligned)
 
 
 # A tie-maker for f16 values in [4, 8), where f16 steps by 2^-8 and f32
@@ -179,15 +188,16 @@ def test_f16_slices_follow_the_full_tensors_blocks() -> None:
 
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_normal_start_chain_bitwise(dtype) -> None:
-    for numel in _numels(dtype):
+    for numel, misaligned in _numels(dtype):
         ref = torch.empty(numel, device="cuda", dtype=dtype)
         torch.ops.tdx.normal_(ref, 0.2, 1.5, seed=SEED, offset=OFFSET)
         ref.mul_(1.0 / 3.0).sub_(0.7).clamp_(-1.25, 0.5).clamp_max_(0.25)
         assert not ref.isnan().any()
         out = _chain(numel, dtype, 1, 0.2, 1.5,
                      [MUL, SUB, CLAMP, CLAMP_MAX],
-                     [1.0 / 3.0, 0.7, -1.25, 0.25], [0.0, 0.0, 0.5, 0.0])
-        assert torch.equal(out, ref), (dtype, numel)
+                     [1.0 / 3.0, 0.7, -1.25, 0.25], [0.0, 0.0, 0.5, 0.0],
+                     misaligned)
+        assert torch.equal(out, ref), (dtype, numel, misaligned)
 
 
 def test_infinities_reach_the_clamp_bitwise() -> None:

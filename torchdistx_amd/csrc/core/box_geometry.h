@@ -5,9 +5,9 @@
 // A box full[lo_0:hi_0, ..., lo_{r-1}:hi_{r-1}] of a contiguous tensor,
 // flattened in row-major order, is a nest of equally long contiguous runs
 // of the full tensor's element space. BoxGeometry is that nest in its
-// smallest form; the windowed slice of one dim (ShardWindow in
-// deferred_init.cc) is its one-level case and a flat range its zero-level
-// case.
+// smallest form; the windowed slice of one dim is its one-level case and a
+// flat range a single run (no level, or levels of extent 1). The slice and
+// block paths of deferred_init.cc and every window and box op carry it.
 
 #pragma once
 
@@ -200,6 +200,23 @@ inline const char* checkBoxArgs(const int64_t* extents, size_t n_extents,
     return "the box does not fit in full_numel";
   }
   return nullptr;
+}
+
+// The geometry that op arguments describe: `levels` (at most
+// kMaxBoxLevels, as checkBoxArgs ensures) extents and strides, outermost
+// first. A single-dim window is boxFromArgs(&n_blocks, &g_stride, 1, ...).
+inline BoxGeometry boxFromArgs(const int64_t* extents,
+                               const int64_t* g_strides, size_t levels,
+                               int64_t run_len, int64_t g_off) {
+  BoxGeometry geo;
+  geo.g_off = g_off;
+  geo.run_len = run_len;
+  geo.levels = static_cast<int32_t>(levels);
+  for (size_t l = 0; l < levels; ++l) {
+    geo.extent[l] = extents[l];
+    geo.g_stride[l] = g_strides[l];
+  }
+  return geo;
 }
 
 // Rows [first, last) of a box.

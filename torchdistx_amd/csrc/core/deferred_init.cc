@@ -1604,53 +1604,52 @@ ChainStep classifyChainNode(const OpNode& node) {
   return step;
 }
 
-// A dim-d slice of a contiguous tensor, flattened: n_blocks contiguous
-// global element ranges of block_len elements, block r starting at
-// g_off + r * g_stride. dim 0 is the n_blocks == 1 case and takes the
-// flat shard ops (whose boundary handling is tuned for it); dim > 0
-// takes the windowed ops.
-struct ShardWindow {
-  int64_t n_blocks;
-  int64_t block_len;
-  int64_t g_stride;
-  int64_t g_off;
-  // Set for an N-d box of two or more levels (materializeTensorBlock),
-  // which takes tdx::rng_box_; the four fields above are then unused.
-  std::optional<BoxGeometry> box = std::nullopt;
+// The slice and block paths describe what they materialize as a
+// BoxGeometry (csrc/core/box_geometry.h) with at least one level. Which
+// ops serve it follows from its shape alone: a single run (a dim-0 slice;
+// one level of extent 1) takes the flat shard ops, whose boundary
+// handling is tuned for it; one strided level (a dim > 0 slice) takes the
+// windowed ops; two or more levels take tdx::rng_box_.
+bool isMultiLevelBox(const BoxGeometry& box) { return box.levels >= 2; }
+
+bool isSingleRun(const BoxGeometry& box) {
+  return box.levels == 1 && box.extent[0] == 1;
+}
+
+template <typename Sig>
+c10::TypedOperatorHandle<Sig> tdxOp(const char* name) {
+  return c10::Dispatcher::singleton()
+      .findSchemaOrThrow(name, "")
+      .typed<Sig>();
+}
+
+using PhiloxState = std::optional<std::pair<uint64_t, uint64_t>>;
+
+void requirePinnedPhilox(const PhiloxState& philox) {
+  TORCH_CHECK(philox.has_value(),
+              "slice materialization: this RNG op carries no pinned "
+              "Philox state (was it recorded by an older build?)");
+}
+
+// A fused tail as the ops take it: parallel lists of opcodes and scalars.
+struct TailArgs {
+  std::vector<int64_t> ops;
+  std::vector<double> s0;
+  std::vector<double> s1;
+
+  explicit TailArgs(const std::vector<TailOp>& tail) {
+    for (const TailOp& t : tail) {
+      ops.push_back(t.op);
+      s0.push_back(t.s0);
+      s1.push_back(t.s1);
+    }
+  }
 };
 
 int64_t rngDistCode(ChainStep::Kind kind) {
   return kind == ChainStep::Kind::kUniform
              ? 0
              : (kind == ChainStep::Kind::kNormal ? 1 : 2);
-}
-
-// One tdx::rng_box_ launch: the RNG step over the box, with `tail` (may
-// be empty) applied before the store.
-void applyBoxStep(const ChainStep& rng, const std::vector<TailOp>& tail,
-                  at::Tensor& shard, const BoxGeometry& box,
-                  int64_t full_numel) {
-  static const auto rng_box =
-      c10::Dispatcher::singleton()
-          .findSchemaOrThrow("tdx::rng_box_", "")
-          .typed<at::Tensor&(at::Tensor&, at::IntArrayRef, at::IntArrayRef,
-                             int64_t, int64_t, int64_t, double, double,
-                             at::IntArrayRef, at::ArrayRef<double>,
-                             at::ArrayRef<double>, int64_t, int64_t,
-                             int64_t)>();
-  std::vector<int64_t> ops;
-  std::vector<double> s0;
-  std::vector<double> s1;
-  for (const TailOp& t : tail) {
-    ops.push_back(t.op);
-    s0.push_back(t.s0);
-    s1.push_back(t.s1);
-  }
-  rng_box.call(shard, at::IntArrayRef(box.extent, box.levels),
-               at::IntArrayRef(box.g_stride, box.levels), box.run_len,
-               box.g_off, rngDistCode(rng.kind), rng.p0, rng.p1, ops, s0, s1,
-               full_numel, static_cast<int64_t>(rng.philox->first),
-               static_cast<int64_t>(rng.philox->second));
 }
 
 // dist code of a value step in the _DIST_CODE numbering of the batched
@@ -1672,46 +1671,114 @@ int64_t valueDistCode(ChainStep::Kind kind) {
 }
 
 // One tdx::patch_box_ call: the value step (dist, p0, p1, philox) on flat
-// elements [lo, lo + len) of the full tensor, applied to what the window
-// (or box) `w` holds of them, at the shard's dtype.
-void applyPatchOp(at::Tensor& shard, const ShardWindow& w, int64_t full_numel,
-                  int64_t lo, int64_t len, int64_t dist, double p0, double p1,
-                  const std::optional<std::pair<uint64_t, uint64_t>>& philox) {
+// elements [lo, lo + len) of the full tensor, applied to what `box` holds
+// of them, at the shard's dtype.
+void applyPatchOp(at::Tensor& shard, const BoxGeometry& box,
+                  int64_t full_numel, int64_t lo, int64_t len, int64_t dist,
+                  double p0, double p1, const PhiloxState& philox) {
   static const auto patch_box =
-      c10::Dispatcher::singleton()
-          .findSchemaOrThrow("tdx::patch_box_", "")
-          .typed<at::Tensor&(at::Tensor&, at::IntArrayRef, at::IntArrayRef,
-                             int64_t, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, double, double, std::optional<int64_t>,
-                             std::optional<int64_t>)>();
-  TORCH_CHECK(dist > 2 || philox.has_value(),
-              "slice materialization: this RNG op carries no pinned "
-              "Philox state (was it recorded by an older build?)");
+      tdxOp<at::Tensor&(at::Tensor&, at::IntArrayRef, at::IntArrayRef,
+                        int64_t, int64_t, int64_t, int64_t, int64_t, int64_t,
+                        double, double, std::optional<int64_t>,
+                        std::optional<int64_t>)>("tdx::patch_box_");
   std::optional<int64_t> seed;
   std::optional<int64_t> offset;
+  if (dist <= 2) {
+    requirePinnedPhilox(philox);
+  }
   if (philox.has_value()) {
     seed = static_cast<int64_t>(philox->first);
     offset = static_cast<int64_t>(philox->second);
   }
-  if (w.box.has_value()) {
-    const BoxGeometry& box = *w.box;
-    patch_box.call(shard, at::IntArrayRef(box.extent, box.levels),
-                   at::IntArrayRef(box.g_stride, box.levels), box.run_len,
-                   box.g_off, full_numel, lo, len, dist, p0, p1, seed, offset);
+  patch_box.call(shard, at::IntArrayRef(box.extent, box.levels),
+                 at::IntArrayRef(box.g_stride, box.levels), box.run_len,
+                 box.g_off, full_numel, lo, len, dist, p0, p1, seed, offset);
+}
+
+// One launch for an RNG step and the fusable tail after it (may be
+// empty): the window or box op draws the values and applies the tail
+// before its single store.
+void applyFusedShardStep(const ChainStep& rng, const std::vector<TailOp>& tail,
+                         at::Tensor& shard, const BoxGeometry& box,
+                         int64_t full_numel) {
+  requirePinnedPhilox(rng.philox);
+  const TailArgs t(tail);
+  const auto seed = static_cast<int64_t>(rng.philox->first);
+  const auto offset = static_cast<int64_t>(rng.philox->second);
+  if (isMultiLevelBox(box)) {
+    static const auto rng_box =
+        tdxOp<at::Tensor&(at::Tensor&, at::IntArrayRef, at::IntArrayRef,
+                          int64_t, int64_t, int64_t, double, double,
+                          at::IntArrayRef, at::ArrayRef<double>,
+                          at::ArrayRef<double>, int64_t, int64_t, int64_t)>(
+            "tdx::rng_box_");
+    rng_box.call(shard, at::IntArrayRef(box.extent, box.levels),
+                 at::IntArrayRef(box.g_stride, box.levels), box.run_len,
+                 box.g_off, rngDistCode(rng.kind), rng.p0, rng.p1, t.ops,
+                 t.s0, t.s1, full_numel, seed, offset);
     return;
   }
-  // A flat range or single-dim window is the one-level box it is.
-  const int64_t extent = w.n_blocks;
-  const int64_t stride = std::max(w.g_stride, w.block_len);
-  patch_box.call(shard, at::IntArrayRef(&extent, 1),
-                 at::IntArrayRef(&stride, 1), w.block_len, w.g_off,
-                 full_numel, lo, len, dist, p0, p1, seed, offset);
+  static const auto chain_shard_win =
+      tdxOp<at::Tensor&(at::Tensor&, int64_t, int64_t, int64_t, int64_t,
+                        int64_t, double, double, at::IntArrayRef,
+                        at::ArrayRef<double>, at::ArrayRef<double>, int64_t,
+                        int64_t, int64_t)>("tdx::rng_chain_shard_win_");
+  chain_shard_win.call(shard, box.extent[0], box.run_len, box.g_stride[0],
+                       box.g_off, rngDistCode(rng.kind), rng.p0, rng.p1,
+                       t.ops, t.s0, t.s1, full_numel, seed, offset);
+}
+
+// An RNG step on its own: the flat, window or box op of the step's
+// distribution.
+void applyRngShardStep(const ChainStep& step, at::Tensor& shard,
+                       const BoxGeometry& box, int64_t full_numel) {
+  if (isMultiLevelBox(box)) {
+    applyFusedShardStep(step, {}, shard, box, full_numel);
+    return;
+  }
+  requirePinnedPhilox(step.philox);
+  // (from, to) / (mean, std) ops and the one-parameter bernoulli ops.
+  using Flat2 = at::Tensor&(at::Tensor&, int64_t, int64_t, double, double,
+                            int64_t, int64_t);
+  using Flat1 = at::Tensor&(at::Tensor&, int64_t, int64_t, double, int64_t,
+                            int64_t);
+  using Win2 = at::Tensor&(at::Tensor&, int64_t, int64_t, int64_t, int64_t,
+                           double, double, int64_t, int64_t);
+  using Win1 = at::Tensor&(at::Tensor&, int64_t, int64_t, int64_t, int64_t,
+                           double, int64_t, int64_t);
+  static const auto uniform_shard = tdxOp<Flat2>("tdx::uniform_shard_");
+  static const auto normal_shard = tdxOp<Flat2>("tdx::normal_shard_");
+  static const auto bernoulli_shard = tdxOp<Flat1>("tdx::bernoulli_shard_");
+  static const auto uniform_win = tdxOp<Win2>("tdx::uniform_shard_win_");
+  static const auto normal_win = tdxOp<Win2>("tdx::normal_shard_win_");
+  static const auto bernoulli_win = tdxOp<Win1>("tdx::bernoulli_shard_win_");
+  const auto seed = static_cast<int64_t>(step.philox->first);
+  const auto offset = static_cast<int64_t>(step.philox->second);
+  const bool bernoulli = step.kind == ChainStep::Kind::kBernoulli;
+  const bool uniform = step.kind == ChainStep::Kind::kUniform;
+  if (isSingleRun(box)) {
+    const int64_t start = box.g_off;
+    const int64_t end = box.g_off + box.run_len;
+    if (bernoulli) {
+      bernoulli_shard.call(shard, start, end, step.p0, seed, offset);
+    } else {
+      (uniform ? uniform_shard : normal_shard)
+          .call(shard, start, end, step.p0, step.p1, seed, offset);
+    }
+  } else if (bernoulli) {
+    bernoulli_win.call(shard, box.extent[0], box.run_len, box.g_stride[0],
+                       box.g_off, step.p0, seed, offset);
+  } else {
+    (uniform ? uniform_win : normal_win)
+        .call(shard, box.extent[0], box.run_len, box.g_stride[0], box.g_off,
+              step.p0, step.p1, seed, offset);
+  }
 }
 
 void applyShardStep(const ChainStep& step, at::Tensor& shard,
-                    const ShardWindow& w, int64_t full_numel) {
+                    const BoxGeometry& box, int64_t full_numel) {
   if (step.patch) {
-    applyPatchOp(shard, w, full_numel, step.patch_lo, step.patch_len,
+    applyPatchOp(shard, box, full_numel, step.patch_lo, step.patch_len,
                  valueDistCode(step.kind), step.p0, step.p1, step.philox);
     return;
   }
@@ -1743,137 +1810,32 @@ void applyShardStep(const ChainStep& step, at::Tensor& shard,
       return;
     case ChainStep::Kind::kUniform:
     case ChainStep::Kind::kNormal:
-    case ChainStep::Kind::kBernoulli: {
-      TORCH_CHECK(step.philox.has_value(),
-                  "slice materialization: this RNG op carries no pinned "
-                  "Philox state (was it recorded by an older build?)");
-      if (w.box.has_value()) {
-        applyBoxStep(step, {}, shard, *w.box, full_numel);
-        return;
-      }
-      static const auto uniform_shard =
-          c10::Dispatcher::singleton()
-              .findSchemaOrThrow("tdx::uniform_shard_", "")
-              .typed<at::Tensor&(at::Tensor&, int64_t, int64_t, double,
-                                 double, int64_t, int64_t)>();
-      static const auto normal_shard =
-          c10::Dispatcher::singleton()
-              .findSchemaOrThrow("tdx::normal_shard_", "")
-              .typed<at::Tensor&(at::Tensor&, int64_t, int64_t, double,
-                                 double, int64_t, int64_t)>();
-      static const auto bernoulli_shard =
-          c10::Dispatcher::singleton()
-              .findSchemaOrThrow("tdx::bernoulli_shard_", "")
-              .typed<at::Tensor&(at::Tensor&, int64_t, int64_t, double,
-                                 int64_t, int64_t)>();
-      static const auto uniform_shard_win =
-          c10::Dispatcher::singleton()
-              .findSchemaOrThrow("tdx::uniform_shard_win_", "")
-              .typed<at::Tensor&(at::Tensor&, int64_t, int64_t, int64_t,
-                                 int64_t, double, double, int64_t,
-                                 int64_t)>();
-      static const auto normal_shard_win =
-          c10::Dispatcher::singleton()
-              .findSchemaOrThrow("tdx::normal_shard_win_", "")
-              .typed<at::Tensor&(at::Tensor&, int64_t, int64_t, int64_t,
-                                 int64_t, double, double, int64_t,
-                                 int64_t)>();
-      static const auto bernoulli_shard_win =
-          c10::Dispatcher::singleton()
-              .findSchemaOrThrow("tdx::bernoulli_shard_win_", "")
-              .typed<at::Tensor&(at::Tensor&, int64_t, int64_t, int64_t,
-                                 int64_t, double, int64_t, int64_t)>();
-      const auto& [seed, offset] = *step.philox;
-      const auto s64 = static_cast<int64_t>(seed);
-      const auto o64 = static_cast<int64_t>(offset);
-      if (w.n_blocks == 1) {
-        const int64_t start = w.g_off;
-        const int64_t end = w.g_off + w.block_len;
-        if (step.kind == ChainStep::Kind::kUniform) {
-          uniform_shard.call(shard, start, end, step.p0, step.p1, s64, o64);
-        } else if (step.kind == ChainStep::Kind::kNormal) {
-          normal_shard.call(shard, start, end, step.p0, step.p1, s64, o64);
-        } else {
-          bernoulli_shard.call(shard, start, end, step.p0, s64, o64);
-        }
-      } else if (step.kind == ChainStep::Kind::kUniform) {
-        uniform_shard_win.call(shard, w.n_blocks, w.block_len, w.g_stride,
-                               w.g_off, step.p0, step.p1, s64, o64);
-      } else if (step.kind == ChainStep::Kind::kNormal) {
-        normal_shard_win.call(shard, w.n_blocks, w.block_len, w.g_stride,
-                              w.g_off, step.p0, step.p1, s64, o64);
-      } else {
-        bernoulli_shard_win.call(shard, w.n_blocks, w.block_len, w.g_stride,
-                                 w.g_off, step.p0, s64, o64);
-      }
+    case ChainStep::Kind::kBernoulli:
+      applyRngShardStep(step, shard, box, full_numel);
       return;
-    }
   }
-}
-
-// One launch for an RNG step and the fusable tail after it: the window
-// (or box) op draws the values and applies the tail before its single
-// store.
-void applyFusedShardStep(const ChainStep& rng, const std::vector<TailOp>& tail,
-                         at::Tensor& shard, const ShardWindow& w,
-                         int64_t full_numel) {
-  TORCH_CHECK(rng.philox.has_value(),
-              "slice materialization: this RNG op carries no pinned "
-              "Philox state (was it recorded by an older build?)");
-  if (w.box.has_value()) {
-    applyBoxStep(rng, tail, shard, *w.box, full_numel);
-    return;
-  }
-  static const auto chain_shard_win =
-      c10::Dispatcher::singleton()
-          .findSchemaOrThrow("tdx::rng_chain_shard_win_", "")
-          .typed<at::Tensor&(at::Tensor&, int64_t, int64_t, int64_t, int64_t,
-                             int64_t, double, double, at::IntArrayRef,
-                             at::ArrayRef<double>, at::ArrayRef<double>,
-                             int64_t, int64_t, int64_t)>();
-  std::vector<int64_t> ops;
-  std::vector<double> s0;
-  std::vector<double> s1;
-  for (const TailOp& t : tail) {
-    ops.push_back(t.op);
-    s0.push_back(t.s0);
-    s1.push_back(t.s1);
-  }
-  chain_shard_win.call(shard, w.n_blocks, w.block_len, w.g_stride, w.g_off,
-                       rngDistCode(rng.kind), rng.p0, rng.p1, ops, s0, s1,
-                       full_numel, static_cast<int64_t>(rng.philox->first),
-                       static_cast<int64_t>(rng.philox->second));
 }
 
 // applyFusedShardStep for a chain that ends in a conversion: `shard` has
 // the FINAL dtype, the values are drawn (and the tail applied) at
-// `src_dtype`. Windows only; boxes convert a temporary (replayChainOnShard).
+// `src_dtype`. Single runs and windows only; boxes of two or more levels
+// convert a temporary (replayChainOnShard).
 void applyFusedCastShardStep(const ChainStep& rng,
                              const std::vector<TailOp>& tail,
                              c10::ScalarType src_dtype, at::Tensor& shard,
-                             const ShardWindow& w, int64_t full_numel) {
-  TORCH_CHECK(rng.philox.has_value(),
-              "slice materialization: this RNG op carries no pinned "
-              "Philox state (was it recorded by an older build?)");
+                             const BoxGeometry& box, int64_t full_numel) {
+  requirePinnedPhilox(rng.philox);
   static const auto chain_cast_shard_win =
-      c10::Dispatcher::singleton()
-          .findSchemaOrThrow("tdx::rng_chain_cast_shard_win_", "")
-          .typed<at::Tensor&(at::Tensor&, at::ScalarType, int64_t, int64_t,
-                             int64_t, int64_t, int64_t, double, double,
-                             at::IntArrayRef, at::ArrayRef<double>,
-                             at::ArrayRef<double>, int64_t, int64_t,
-                             int64_t)>();
-  std::vector<int64_t> ops;
-  std::vector<double> s0;
-  std::vector<double> s1;
-  for (const TailOp& t : tail) {
-    ops.push_back(t.op);
-    s0.push_back(t.s0);
-    s1.push_back(t.s1);
-  }
-  chain_cast_shard_win.call(shard, src_dtype, w.n_blocks, w.block_len,
-                            w.g_stride, w.g_off, rngDistCode(rng.kind),
-                            rng.p0, rng.p1, ops, s0, s1, full_numel,
+      tdxOp<at::Tensor&(at::Tensor&, at::ScalarType, int64_t, int64_t,
+                        int64_t, int64_t, int64_t, double, double,
+                        at::IntArrayRef, at::ArrayRef<double>,
+                        at::ArrayRef<double>, int64_t, int64_t, int64_t)>(
+          "tdx::rng_chain_cast_shard_win_");
+  const TailArgs t(tail);
+  chain_cast_shard_win.call(shard, src_dtype, box.extent[0], box.run_len,
+                            box.g_stride[0], box.g_off,
+                            rngDistCode(rng.kind), rng.p0, rng.p1, t.ops,
+                            t.s0, t.s1, full_numel,
                             static_cast<int64_t>(rng.philox->first),
                             static_cast<int64_t>(rng.philox->second));
 }
@@ -2369,10 +2331,10 @@ std::optional<ChainPlan> chainPlanImpl(const at::Tensor& tensor,
 }
 
 // Allocates the shard and applies the tensor's init chain to it over the
-// window (or box) `w` of the full tensor.
+// box `w` of the full tensor.
 at::Tensor replayChainOnShard(FakeTensorImpl* fake,
                               const std::vector<int64_t>& shard_sizes,
-                              const ShardWindow& w) {
+                              const BoxGeometry& w) {
   const at::Tensor& meta = fake->meta_tensor();
   std::lock_guard<std::recursive_mutex> lock{tape_mutex};
   auto rec = getRecord(fake);
@@ -2413,7 +2375,7 @@ at::Tensor replayChainOnShard(FakeTensorImpl* fake,
   // before the conversion with its value rounded through the source dtype
   // first; an RNG patch draws at the dtype it was recorded at, so a chain
   // with one takes the segments.
-  if (!w.box.has_value() && !rng_patch) {
+  if (!isMultiLevelBox(w) && !rng_patch) {
     const auto run = fusedRunStart(plain, 0, plain.size(), meta.numel(),
                                    /*allow_cast=*/true);
     if (run.has_value() && run->cast.has_value()) {
@@ -2551,8 +2513,10 @@ at::Tensor materializeTensorShard(const at::Tensor& tensor,
   for (int64_t d = 0; d < dim; ++d) {
     n_blocks *= meta.size(d);
   }
-  const ShardWindow w{n_blocks, (end_row - start_row) * inner,
-                      dim_len * inner, start_row * inner};
+  const int64_t g_stride = dim_len * inner;
+  const BoxGeometry w =
+      boxFromArgs(&n_blocks, &g_stride, 1, (end_row - start_row) * inner,
+                  start_row * inner);
 
   std::vector<int64_t> shard_sizes(meta.sizes().begin(), meta.sizes().end());
   if (!shard_sizes.empty()) {
@@ -2592,16 +2556,14 @@ at::Tensor materializeTensorBlock(const at::Tensor& tensor,
               "slice materialization: the block needs more than ",
               kMaxBoxLevels, " nested strided levels; materialize the "
               "tensor fully instead.");
-  // 0 and 1 levels are the flat range and the single-dim window, served
-  // by the ops materializeTensorShard launches; deeper nests take the box
-  // op.
-  ShardWindow w{1, box.run_len, box.run_len, box.g_off};
-  if (box.levels == 1) {
-    w = ShardWindow{box.extent[0], box.run_len, box.g_stride[0], box.g_off};
-  } else if (box.levels >= 2) {
-    w.box = box;
+  // A flat range (or an empty block) normalizes to no level; the replay
+  // takes it as one run.
+  if (box.levels == 0) {
+    box.levels = 1;
+    box.extent[0] = 1;
+    box.g_stride[0] = box.run_len;
   }
-  return replayChainOnShard(fake, shard_sizes, w);
+  return replayChainOnShard(fake, shard_sizes, box);
 }
 
 at::Tensor materializeTensor(const at::Tensor& tensor) {

@@ -118,6 +118,25 @@ void cpuPhiloxRange(T* out, int64_t start, int64_t end, float a, float b,
   }
 }
 
+// Calls f(T*) with the tensor's data pointer at its element type.
+template <typename F>
+void dispatchFloat3(at::Tensor& t, F&& f) {
+  switch (t.scalar_type()) {
+    case at::kFloat:
+      f(t.data_ptr<float>());
+      break;
+    case at::kBFloat16:
+      f(t.data_ptr<at::BFloat16>());
+      break;
+    case at::kHalf:
+      f(t.data_ptr<at::Half>());
+      break;
+    default:
+      TORCH_CHECK(false, "tdx init supports float32/bf16/fp16, got ",
+                  t.scalar_type());
+  }
+}
+
 template <RngKind kKind>
 void cpuPhiloxDispatch(at::Tensor& self, int64_t start, int64_t end,
                        float a, float b, uint64_t seed, uint64_t offset) {
@@ -125,23 +144,10 @@ void cpuPhiloxDispatch(at::Tensor& self, int64_t start, int64_t end,
               "tdx CPU init requires contiguous tensors");
   TORCH_CHECK(self.numel() == end - start,
               "shard numel must equal end - start");
-  switch (self.scalar_type()) {
-    case at::kFloat:
-      cpuPhiloxRange<float, kKind>(self.data_ptr<float>(), start, end, a,
-                                     b, seed, offset);
-      break;
-    case at::kBFloat16:
-      cpuPhiloxRange<at::BFloat16, kKind>(self.data_ptr<at::BFloat16>(),
-                                            start, end, a, b, seed, offset);
-      break;
-    case at::kHalf:
-      cpuPhiloxRange<at::Half, kKind>(self.data_ptr<at::Half>(), start,
-                                        end, a, b, seed, offset);
-      break;
-    default:
-      TORCH_CHECK(false, "tdx init supports float32/bf16/fp16, got ",
-                  self.scalar_type());
-  }
+  dispatchFloat3(self, [&](auto* out) {
+    using T = std::remove_pointer_t<decltype(out)>;
+    cpuPhiloxRange<T, kKind>(out, start, end, a, b, seed, offset);
+  });
 }
 
 // ---- CPU impls of the full-tensor ops -------------------------------------
@@ -235,16 +241,64 @@ at::Tensor& cpu_bernoulli_shard_(at::Tensor& shard, int64_t start,
   return shard;
 }
 
+// N-d box (csrc/core/box_geometry.h): the shard is rows() runs of run_len
+// contiguous global elements each, so the CPU form is the flat range fill
+// once per run. Same counter layout as the flat range, so each run is
+// bitwise the matching stretch of the full tensor. CUDA twin:
+// csrc/hip/init_kernels.hip rng_box_kernel.
+template <RngKind kKind>
+void cpuPhiloxBox(at::Tensor& shard, const BoxGeometry& geo, float a,
+                  float b, uint64_t seed, uint64_t offset) {
+  dispatchFloat3(shard, [&](auto* out) {
+    using T = std::remove_pointer_t<decltype(out)>;
+    const int64_t rows = geo.rows();
+    for (int64_t r = 0; r < rows; ++r) {
+      const int64_t lo = geo.rowStart(r);
+      cpuPhiloxRange<T, kKind>(out + r * geo.run_len, lo, lo + geo.run_len,
+                               a, b, seed, offset);
+    }
+  });
+}
+
+// The RNG step of the window, chain and box ops: dist 0 uniform(p0, p1),
+// 1 normal(p0, p1), 2 bernoulli(p0). `what` names the op in the error for
+// any other code.
+void cpuRngBox(at::Tensor& shard, const BoxGeometry& geo, int64_t dist,
+               double p0, double p1, int64_t seed, int64_t offset,
+               const char* what) {
+  const auto a = static_cast<float>(p0);
+  const auto s = static_cast<uint64_t>(seed);
+  const auto o = static_cast<uint64_t>(offset);
+  switch (dist) {
+    case 0:
+      cpuPhiloxBox<RngKind::kUniform>(shard, geo, a,
+                                      static_cast<float>(p1 - p0), s, o);
+      break;
+    case 1:
+      TORCH_CHECK(p1 >= 0.0, "normal_ expects std >= 0.0, but found std=",
+                  p1);
+      cpuPhiloxBox<RngKind::kNormal>(shard, geo, a, static_cast<float>(p1),
+                                     s, o);
+      break;
+    case 2:
+      TORCH_CHECK(0.0 <= p0 && p0 <= 1.0,
+                  "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
+      cpuPhiloxBox<RngKind::kBernoulli>(shard, geo, a, 0.0f, s, o);
+      break;
+    default:
+      TORCH_CHECK(false, what, ": dist must be 0 (uniform), 1 (normal) or 2 "
+                               "(bernoulli), got ", dist);
+  }
+}
+
 // Windowed shard (any-dim slices): the shard is n_blocks contiguous
 // global ranges of block_len elements, block r starting at global
-// element g_off + r * g_stride — `full.narrow(dim, s, len)` flattened.
-// Same counter layout as the flat range, so each block is bitwise the
-// matching stretch of the full tensor (CUDA twin:
-// csrc/hip/init_kernels.hip rng_shard_window_kernel).
-template <RngKind kKind>
-void cpuPhiloxWindow(at::Tensor& shard, int64_t n_blocks, int64_t block_len,
-                     int64_t g_stride, int64_t g_off, float a, float b,
-                     uint64_t seed, uint64_t offset) {
+// element g_off + r * g_stride — `full.narrow(dim, s, len)` flattened,
+// a one-level box.
+at::Tensor& cpuRngWindow(at::Tensor& shard, int64_t n_blocks,
+                         int64_t block_len, int64_t g_stride, int64_t g_off,
+                         int64_t dist, double p0, double p1, int64_t seed,
+                         int64_t offset) {
   TORCH_CHECK(shard.is_contiguous(),
               "tdx CPU init requires contiguous tensors");
   TORCH_CHECK(n_blocks >= 0 && block_len >= 0 && g_stride >= block_len &&
@@ -252,60 +306,33 @@ void cpuPhiloxWindow(at::Tensor& shard, int64_t n_blocks, int64_t block_len,
               "invalid shard window");
   TORCH_CHECK(shard.numel() == n_blocks * block_len,
               "shard numel must equal n_blocks * block_len");
-  auto run = [&](auto* out) {
-    using T = std::remove_pointer_t<decltype(out)>;
-    for (int64_t r = 0; r < n_blocks; ++r) {
-      const int64_t lo = g_off + r * g_stride;
-      cpuPhiloxRange<T, kKind>(out + r * block_len, lo, lo + block_len, a,
-                               b, seed, offset);
-    }
-  };
-  switch (shard.scalar_type()) {
-    case at::kFloat:
-      run(shard.data_ptr<float>());
-      break;
-    case at::kBFloat16:
-      run(shard.data_ptr<at::BFloat16>());
-      break;
-    case at::kHalf:
-      run(shard.data_ptr<at::Half>());
-      break;
-    default:
-      TORCH_CHECK(false, "tdx CPU init supports float32/bf16/fp16, got ",
-                  shard.scalar_type());
-  }
+  cpuRngBox(shard, boxFromArgs(&n_blocks, &g_stride, 1, block_len, g_off),
+            dist, p0, p1, seed, offset, "rng_chain");
+  return shard;
 }
 
 at::Tensor& cpu_uniform_shard_win_(at::Tensor& shard, int64_t n_blocks,
                                    int64_t block_len, int64_t g_stride,
                                    int64_t g_off, double from, double to,
                                    int64_t seed, int64_t offset) {
-  cpuPhiloxWindow<RngKind::kUniform>(
-      shard, n_blocks, block_len, g_stride, g_off, static_cast<float>(from),
-      static_cast<float>(to - from), static_cast<uint64_t>(seed),
-      static_cast<uint64_t>(offset));
-  return shard;
+  return cpuRngWindow(shard, n_blocks, block_len, g_stride, g_off, 0, from,
+                      to, seed, offset);
 }
 
 at::Tensor& cpu_normal_shard_win_(at::Tensor& shard, int64_t n_blocks,
                                   int64_t block_len, int64_t g_stride,
                                   int64_t g_off, double mean, double std,
                                   int64_t seed, int64_t offset) {
-  cpuPhiloxWindow<RngKind::kNormal>(
-      shard, n_blocks, block_len, g_stride, g_off, static_cast<float>(mean),
-      static_cast<float>(std), static_cast<uint64_t>(seed),
-      static_cast<uint64_t>(offset));
-  return shard;
+  return cpuRngWindow(shard, n_blocks, block_len, g_stride, g_off, 1, mean,
+                      std, seed, offset);
 }
 
 at::Tensor& cpu_bernoulli_shard_win_(at::Tensor& shard, int64_t n_blocks,
                                      int64_t block_len, int64_t g_stride,
                                      int64_t g_off, double p, int64_t seed,
                                      int64_t offset) {
-  cpuPhiloxWindow<RngKind::kBernoulli>(
-      shard, n_blocks, block_len, g_stride, g_off, static_cast<float>(p),
-      0.0f, static_cast<uint64_t>(seed), static_cast<uint64_t>(offset));
-  return shard;
+  return cpuRngWindow(shard, n_blocks, block_len, g_stride, g_off, 2, p, 0.0,
+                      seed, offset);
 }
 
 // ---- fused RNG + pointwise-tail ops ---------------------------------------
@@ -376,56 +403,13 @@ at::Tensor& cpu_rng_chain_shard_win_(
   // GPU kernels; ATen's CPU kernels have none.
   (void)full_numel;
   cpuCheckTail(tail_ops, tail_s0, tail_s1);
-  switch (dist) {
-    case 0:
-      cpu_uniform_shard_win_(shard, n_blocks, block_len, g_stride, g_off, p0,
-                             p1, seed, offset);
-      break;
-    case 1:
-      cpu_normal_shard_win_(shard, n_blocks, block_len, g_stride, g_off, p0,
-                            p1, seed, offset);
-      break;
-    case 2:
-      cpu_bernoulli_shard_win_(shard, n_blocks, block_len, g_stride, g_off,
-                               p0, seed, offset);
-      break;
-    default:
-      TORCH_CHECK(false, "rng_chain: dist must be 0 (uniform), 1 (normal) "
-                         "or 2 (bernoulli), got ", dist);
-  }
+  cpuRngWindow(shard, n_blocks, block_len, g_stride, g_off, dist, p0, p1,
+               seed, offset);
   cpuApplyTail(shard, tail_ops, tail_s0, tail_s1);
   return shard;
 }
 
-// N-d box (csrc/core/box_geometry.h): the shard is prod(extents) runs of
-// run_len contiguous global elements each, so the CPU form is the flat
-// range fill once per run, then the tail ops on the shard. CUDA twin:
-// csrc/hip/init_kernels.hip rng_box_kernel.
-template <RngKind kKind>
-void cpuPhiloxBox(at::Tensor& shard, const BoxGeometry& geo, float a,
-                  float b, uint64_t seed, uint64_t offset) {
-  auto run = [&](auto* out) {
-    using T = std::remove_pointer_t<decltype(out)>;
-    const int64_t rows = geo.rows();
-    for (int64_t r = 0; r < rows; ++r) {
-      const int64_t lo = geo.rowStart(r);
-      cpuPhiloxRange<T, kKind>(out + r * geo.run_len, lo, lo + geo.run_len,
-                               a, b, seed, offset);
-    }
-  };
-  switch (shard.scalar_type()) {
-    case at::kFloat:
-      run(shard.data_ptr<float>());
-      break;
-    case at::kBFloat16:
-      run(shard.data_ptr<at::BFloat16>());
-      break;
-    default:
-      run(shard.data_ptr<at::Half>());
-      break;
-  }
-}
-
+// The box op: the RNG step over the box, then the tail ops on the shard.
 at::Tensor& cpu_rng_box_(at::Tensor& shard, at::IntArrayRef extents,
                          at::IntArrayRef g_strides, int64_t run_len,
                          int64_t g_off, int64_t dist, double p0, double p1,
@@ -445,48 +429,19 @@ at::Tensor& cpu_rng_box_(at::Tensor& shard, at::IntArrayRef extents,
     TORCH_CHECK(TailOp::kErfinv <= op && op <= TailOp::kAbs,
                 "rng_chain: bad tail opcode ", op);
   }
-  TORCH_CHECK(dist != 1 || p1 >= 0.0,
-              "normal_ expects std >= 0.0, but found std=", p1);
-  TORCH_CHECK(dist != 2 || (0.0 <= p0 && p0 <= 1.0),
-              "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
-  TORCH_CHECK(0 <= dist && dist <= 2,
-              "rng_box: dist must be 0 (uniform), 1 (normal) or 2 "
-              "(bernoulli), got ", dist);
   TORCH_CHECK(shard.scalar_type() == at::kFloat ||
                   shard.scalar_type() == at::kBFloat16 ||
                   shard.scalar_type() == at::kHalf,
               "tdx box kernel supports float32/bf16/fp16, got ",
               shard.scalar_type());
-  if (shard.numel() == 0) {
-    return shard;
-  }
-  BoxGeometry geo;
-  geo.g_off = g_off;
-  geo.run_len = run_len;
-  geo.levels = static_cast<int32_t>(extents.size());
-  for (int l = 0; l < geo.levels; ++l) {
-    geo.extent[l] = extents[l];
-    geo.g_stride[l] = g_strides[l];
-  }
-  const auto s = static_cast<uint64_t>(seed);
-  const auto o = static_cast<uint64_t>(offset);
-  switch (dist) {
-    case 0:
-      cpuPhiloxBox<RngKind::kUniform>(shard, geo, static_cast<float>(p0),
-                                      static_cast<float>(p1 - p0), s, o);
-      break;
-    case 1:
-      cpuPhiloxBox<RngKind::kNormal>(shard, geo, static_cast<float>(p0),
-                                     static_cast<float>(p1), s, o);
-      break;
-    default:
-      cpuPhiloxBox<RngKind::kBernoulli>(shard, geo, static_cast<float>(p0),
-                                        0.0f, s, o);
-      break;
-  }
+  cpuRngBox(shard,
+            boxFromArgs(extents.data(), g_strides.data(), extents.size(),
+                        run_len, g_off),
+            dist, p0, p1, seed, offset, "rng_box");
   cpuApplyTail(shard, tail_ops, tail_s0, tail_s1);
   return shard;
 }
+
 
 at::Tensor& cpu_rng_chain_(at::Tensor& self, int64_t dist, double p0,
                            double p1, at::IntArrayRef tail_ops,
@@ -574,14 +529,8 @@ at::Tensor& cpu_patch_box_(at::Tensor& shard, at::IntArrayRef extents,
                   shard.scalar_type() == at::kHalf,
               "tdx patch kernel supports float32/bf16/fp16, got ",
               shard.scalar_type());
-  BoxGeometry geo;
-  geo.g_off = g_off;
-  geo.run_len = run_len;
-  geo.levels = static_cast<int32_t>(extents.size());
-  for (int l = 0; l < geo.levels; ++l) {
-    geo.extent[l] = extents[l];
-    geo.g_stride[l] = g_strides[l];
-  }
+  const BoxGeometry geo = boxFromArgs(extents.data(), g_strides.data(),
+                                      extents.size(), run_len, g_off);
   const int64_t patch_hi = patch_lo + patch_len;
   const RowRange rows = rowsMeeting(geo, patch_lo, patch_hi);
   if (rows.count() == 0) {
@@ -593,7 +542,7 @@ at::Tensor& cpu_patch_box_(at::Tensor& shard, at::IntArrayRef extents,
   const float b = dist == 0 ? static_cast<float>(p1 - p0)
                             : (dist == 1 ? static_cast<float>(p1) : 0.0f);
   at::Tensor flat = shard.view({-1});
-  auto run = [&](auto* out) {
+  dispatchFloat3(shard, [&](auto* out) {
     using T = std::remove_pointer_t<decltype(out)>;
     for (int64_t r = rows.first; r < rows.last; ++r) {
       const int64_t rs = geo.rowStart(r);
@@ -622,18 +571,7 @@ at::Tensor& cpu_patch_box_(at::Tensor& shard, at::IntArrayRef extents,
           break;
       }
     }
-  };
-  switch (shard.scalar_type()) {
-    case at::kFloat:
-      run(shard.data_ptr<float>());
-      break;
-    case at::kBFloat16:
-      run(shard.data_ptr<at::BFloat16>());
-      break;
-    default:
-      run(shard.data_ptr<at::Half>());
-      break;
-  }
+  });
   return shard;
 }
 

@@ -28,7 +28,6 @@
 #include <ATen/hip/HIPGeneratorImpl.h>
 #include <torch/library.h>
 
-#include <cstdlib>
 #include <limits>
 #include <type_traits>
 
@@ -376,6 +375,44 @@ uint64_t acquireSeedOffset(const std::optional<at::Generator>& generator,
   return state.second;
 }
 
+// Calls f(T{}) with the device element type of `t`; `what` names the
+// kernels in the error for any other dtype.
+template <typename F>
+void dispatchFloat3(c10::ScalarType t, const char* what, F&& f) {
+  switch (t) {
+    case at::kFloat:
+      f(float{});
+      break;
+    case at::kBFloat16:
+      f(__hip_bfloat16{});
+      break;
+    case at::kHalf:
+      f(__half{});
+      break;
+    default:
+      TORCH_CHECK(false, what, " support float32/bf16/fp16, got ", t);
+  }
+}
+
+// p0/p1 are (from, to) for uniform, (mean, std) for normal, and
+// (p, unused) for bernoulli; uniform/normal apply a + b * sample,
+// bernoulli thresholds the raw uniform against a.
+struct Affine {
+  float a;
+  float b;
+};
+
+template <Dist kDist>
+Affine affineOf(double p0, double p1) {
+  if constexpr (kDist == Dist::kUniform) {
+    return {static_cast<float>(p0), static_cast<float>(p1 - p0)};
+  } else if constexpr (kDist == Dist::kNormal) {
+    return {static_cast<float>(p0), static_cast<float>(p1)};
+  } else {
+    return {static_cast<float>(p0), 0.0f};
+  }
+}
+
 template <Dist kDist>
 void launchRng(at::Tensor& self,
                double p0,
@@ -400,16 +437,9 @@ void launchRng(at::Tensor& self,
     offset = acquireSeedOffset(generator, &seed);
   }
   auto stream = at::cuda::getCurrentCUDAStream();
-
-  // p0/p1 are (from, to) for uniform, (mean, std) for normal, and
-  // (p, unused) for bernoulli; uniform/normal apply a + b * sample,
-  // bernoulli thresholds the raw uniform against a.
-  float a = static_cast<float>(p0);
-  float b = kDist == Dist::kUniform ? static_cast<float>(p1 - p0)
-                                    : static_cast<float>(p1);
-
-  auto launch = [&](auto type_tag) {
-    using T = decltype(type_tag);
+  const Affine ab = affineOf<kDist>(p0, p1);
+  dispatchFloat3(self.scalar_type(), "tdx RNG init kernels", [&](auto tag) {
+    using T = decltype(tag);
     constexpr int kElems = VecTraits<T>::kElems;
     const int64_t n_full = n / kElems;
     const uint32_t tail = static_cast<uint32_t>(n % kElems);
@@ -419,32 +449,18 @@ void launchRng(at::Tensor& self,
                          dim3(numBlocks(n_groups)), dim3(kBlock), 0,
                          stream.stream(),
                          reinterpret_cast<T*>(self.data_ptr()),
-                         static_cast<uint32_t>(n_full), tail, a, b, seed,
-                         offset);
+                         static_cast<uint32_t>(n_full), tail, ab.a, ab.b,
+                         seed, offset);
     } else {
       hipLaunchKernelGGL((rng_kernel<T, kDist, uint64_t>),
                          dim3(numBlocks(n_groups)), dim3(kBlock), 0,
                          stream.stream(),
                          reinterpret_cast<T*>(self.data_ptr()),
-                         static_cast<uint64_t>(n_full), tail, a, b, seed,
-                         offset);
+                         static_cast<uint64_t>(n_full), tail, ab.a, ab.b,
+                         seed, offset);
     }
     C10_HIP_KERNEL_LAUNCH_CHECK();
-  };
-  switch (self.scalar_type()) {
-    case at::kFloat:
-      launch(float{});
-      break;
-    case at::kBFloat16:
-      launch(__hip_bfloat16{});
-      break;
-    case at::kHalf:
-      launch(__half{});
-      break;
-    default:
-      TORCH_CHECK(false, "tdx RNG init kernels support float32/bf16/fp16, ",
-                  "got ", self.scalar_type());
-  }
+  });
 }
 
 at::Tensor& tdx_uniform_(at::Tensor& self,
@@ -554,37 +570,21 @@ void launchRngShard(at::Tensor& shard,
   if (shard.numel() == 0) {
     return;
   }
-  float a = static_cast<float>(p0);
-  float b = kDist == Dist::kUniform ? static_cast<float>(p1 - p0)
-                                    : static_cast<float>(p1);
+  const Affine ab = affineOf<kDist>(p0, p1);
   auto stream = at::cuda::getCurrentCUDAStream();
-  auto launch = [&](auto type_tag) {
-    using T = decltype(type_tag);
+  dispatchFloat3(shard.scalar_type(), "tdx shard kernels", [&](auto tag) {
+    using T = decltype(tag);
     const int64_t n_groups =
         (end + VecTraits<T>::kElems - 1) / VecTraits<T>::kElems -
         start / VecTraits<T>::kElems;
     hipLaunchKernelGGL((rng_shard_kernel<T, kDist>),
                        dim3(numBlocks(n_groups)), dim3(kBlock), 0,
                        stream.stream(),
-                       reinterpret_cast<T*>(shard.data_ptr()), start, end, a,
-                       b, static_cast<uint64_t>(seed),
+                       reinterpret_cast<T*>(shard.data_ptr()), start, end,
+                       ab.a, ab.b, static_cast<uint64_t>(seed),
                        static_cast<uint64_t>(offset));
     C10_HIP_KERNEL_LAUNCH_CHECK();
-  };
-  switch (shard.scalar_type()) {
-    case at::kFloat:
-      launch(float{});
-      break;
-    case at::kBFloat16:
-      launch(__hip_bfloat16{});
-      break;
-    case at::kHalf:
-      launch(__half{});
-      break;
-    default:
-      TORCH_CHECK(false, "tdx shard kernels support float32/bf16/fp16, got ",
-                  shard.scalar_type());
-  }
+  });
 }
 
 at::Tensor& tdx_uniform_shard_(at::Tensor& shard, int64_t start, int64_t end,
@@ -619,164 +619,6 @@ at::Tensor& tdx_bernoulli_shard_(at::Tensor& shard, int64_t start,
   TORCH_CHECK(0.0 <= p && p <= 1.0,
               "bernoulli_ expects 0 <= p <= 1, but found p=", p);
   launchRngShard<Dist::kBernoulli>(shard, start, end, p, 0.0, seed, offset);
-  return shard;
-}
-
-// Windowed shard kernel: materializes `full.narrow(dim, s, len)` of a
-// contiguous virtual full tensor for any dim — the slice is n_blocks
-// contiguous global ranges of block_len elements, block r starting at
-// global element g_off + r * g_stride (dim 0 is the n_blocks == 1
-// special case, served by rng_shard_kernel above). Shard flat index i
-// maps to global element
-//   g(i) = g_off + (i / block_len) * g_stride + (i % block_len),
-// and the value of global element g is lane g % kElems of Philox group
-// g / kElems — identical to the full-tensor kernel, so any-dim slices
-// are bitwise sub-tensors of the full materialization. When g_off,
-// block_len and g_stride are all group-multiples (the common case:
-// trailing dims of transformer weights are multiples of 8) every group
-// of the window is whole and the destination is 16-byte aligned, so the
-// fast path is group-indexed with vector stores like the flat kernel;
-// odd geometries store elementwise.
-// IdxT is the SHARD-side loop index type: 32-bit up to 2^31 shard
-// groups/elements (the flat-kernel design rule — real shards never pay
-// 64-bit divides, the one VALU-expensive op here); only the GLOBAL
-// group id widens to 64-bit, with a multiply, not a divide.
-template <typename T, Dist kDist, typename IdxT>
-__global__ void rng_shard_window_kernel(T* __restrict__ out,
-                                        IdxT n_blocks,
-                                        IdxT block_len,
-                                        int64_t g_stride,
-                                        int64_t g_off,
-                                        float a,
-                                        float b,
-                                        uint64_t seed,
-                                        uint64_t offset) {
-  constexpr int kElems = VecTraits<T>::kElems;
-  using Vec = typename VecTraits<T>::Vec;
-  const IdxT stride = static_cast<IdxT>(gridDim.x) * blockDim.x;
-  const bool vec_aligned = (g_off % kElems) == 0 &&
-                           (block_len % kElems) == 0 &&
-                           (g_stride % kElems) == 0;
-  if (vec_aligned) {
-    const IdxT gpb = block_len / kElems;  // groups per window block
-    const IdxT n_groups = n_blocks * gpb;
-    const uint64_t g0 = static_cast<uint64_t>(g_off) / kElems;
-    const uint64_t gs = static_cast<uint64_t>(g_stride) / kElems;
-    for (IdxT j = blockIdx.x * static_cast<IdxT>(blockDim.x) + threadIdx.x;
-         j < n_groups; j += stride) {
-      const IdxT blk = j / gpb;
-      const IdxT within = j - blk * gpb;
-      const uint64_t g = g0 + static_cast<uint64_t>(blk) * gs + within;
-      float vals[kElems];
-      rngGroupValues<T, kDist>(g, a, b, seed, offset, vals);
-      Vec v;
-      T* vp = reinterpret_cast<T*>(&v);
-#pragma unroll
-      for (int e = 0; e < kElems; ++e) {
-        vp[e] = from_float<T>(vals[e]);
-      }
-      *reinterpret_cast<Vec*>(out + static_cast<uint64_t>(j) * kElems) = v;
-    }
-    return;
-  }
-  const IdxT n = n_blocks * block_len;
-  for (IdxT i = blockIdx.x * static_cast<IdxT>(blockDim.x) + threadIdx.x;
-       i < n; i += stride) {
-    const IdxT blk = i / block_len;
-    const IdxT rem = i - blk * block_len;
-    const uint64_t ge = static_cast<uint64_t>(g_off) +
-                        static_cast<uint64_t>(blk) * g_stride + rem;
-    const uint64_t g = ge / kElems;
-    float vals[kElems];
-    rngGroupValues<T, kDist>(g, a, b, seed, offset, vals);
-    out[i] = from_float<T>(vals[ge - g * kElems]);
-  }
-}
-
-template <Dist kDist>
-void launchRngShardWindow(at::Tensor& shard, int64_t n_blocks,
-                          int64_t block_len, int64_t g_stride, int64_t g_off,
-                          double p0, double p1, int64_t seed,
-                          int64_t offset) {
-  TORCH_CHECK(shard.is_contiguous(),
-              "tdx shard kernels require contiguous tensors");
-  TORCH_CHECK(n_blocks >= 0 && block_len >= 0 && g_stride >= block_len &&
-                  g_off >= 0,
-              "invalid shard window");
-  TORCH_CHECK(shard.numel() == n_blocks * block_len,
-              "shard numel must equal n_blocks * block_len");
-  if (shard.numel() == 0) {
-    return;
-  }
-  float a = static_cast<float>(p0);
-  float b = kDist == Dist::kUniform ? static_cast<float>(p1 - p0)
-                                    : static_cast<float>(p1);
-  auto stream = at::cuda::getCurrentCUDAStream();
-  auto launch = [&](auto type_tag) {
-    using T = decltype(type_tag);
-    const int64_t n_work =
-        (shard.numel() + VecTraits<T>::kElems - 1) / VecTraits<T>::kElems;
-    auto launch_idx = [&](auto idx_tag) {
-      using IdxT = decltype(idx_tag);
-      hipLaunchKernelGGL((rng_shard_window_kernel<T, kDist, IdxT>),
-                         dim3(numBlocks(n_work)), dim3(kBlock), 0,
-                         stream.stream(),
-                         reinterpret_cast<T*>(shard.data_ptr()),
-                         static_cast<IdxT>(n_blocks),
-                         static_cast<IdxT>(block_len), g_stride, g_off, a,
-                         b, static_cast<uint64_t>(seed),
-                         static_cast<uint64_t>(offset));
-      C10_HIP_KERNEL_LAUNCH_CHECK();
-    };
-    if (shard.numel() <= std::numeric_limits<int32_t>::max()) {
-      launch_idx(uint32_t{});
-    } else {
-      launch_idx(int64_t{});
-    }
-  };
-  switch (shard.scalar_type()) {
-    case at::kFloat:
-      launch(float{});
-      break;
-    case at::kBFloat16:
-      launch(__hip_bfloat16{});
-      break;
-    case at::kHalf:
-      launch(__half{});
-      break;
-    default:
-      TORCH_CHECK(false, "tdx shard kernels support float32/bf16/fp16, got ",
-                  shard.scalar_type());
-  }
-}
-
-at::Tensor& tdx_uniform_shard_win_(at::Tensor& shard, int64_t n_blocks,
-                                   int64_t block_len, int64_t g_stride,
-                                   int64_t g_off, double from, double to,
-                                   int64_t seed, int64_t offset) {
-  launchRngShardWindow<Dist::kUniform>(shard, n_blocks, block_len, g_stride,
-                                       g_off, from, to, seed, offset);
-  return shard;
-}
-
-at::Tensor& tdx_normal_shard_win_(at::Tensor& shard, int64_t n_blocks,
-                                  int64_t block_len, int64_t g_stride,
-                                  int64_t g_off, double mean, double std,
-                                  int64_t seed, int64_t offset) {
-  TORCH_CHECK(std >= 0.0, "normal_ expects std >= 0.0, but found std=", std);
-  launchRngShardWindow<Dist::kNormal>(shard, n_blocks, block_len, g_stride,
-                                      g_off, mean, std, seed, offset);
-  return shard;
-}
-
-at::Tensor& tdx_bernoulli_shard_win_(at::Tensor& shard, int64_t n_blocks,
-                                     int64_t block_len, int64_t g_stride,
-                                     int64_t g_off, double p, int64_t seed,
-                                     int64_t offset) {
-  TORCH_CHECK(0.0 <= p && p <= 1.0,
-              "bernoulli_ expects 0 <= p <= 1, but found p=", p);
-  launchRngShardWindow<Dist::kBernoulli>(shard, n_blocks, block_len, g_stride,
-                                         g_off, p, 0.0, seed, offset);
   return shard;
 }
 
@@ -952,12 +794,25 @@ __device__ __forceinline__ void applyTail(float (&vals)[kElems],
   }
 }
 
-// rng_shard_window_kernel with the tail applied before the store. Same
-// window geometry and index-width rule. The group-indexed vector path
-// additionally serves a single block (n_blocks == 1, the whole-tensor and
-// flat dim-0 case) whose length is not a group multiple: its one partial
-// last group is stored elementwise by one thread. `vec_ok` is the host's
-// check that `out` is 16-byte aligned.
+// The chain kernel of one strided window (checkShardWindow below has the
+// geometry; a whole tensor or a dim-0 shard is the n_blocks == 1 case):
+// shard flat index i is global element
+//   g(i) = g_off + (i / block_len) * g_stride + (i % block_len),
+// whose value is lane g % kElems of Philox group g / kElems — as in the
+// full-tensor kernel — with the tail applied before the store. When
+// g_off, block_len and g_stride are all group multiples every group of
+// the window is whole, and with a 16-byte-aligned `out` (`vec_ok`, checked
+// on the host) the path is group-indexed with vector stores; a single
+// block may then also have a length that is no group multiple, its one
+// partial last group stored elementwise by one thread. Odd geometries
+// store elementwise. IdxT is the SHARD-side index type, 32-bit below 2^31
+// shard elements; only the GLOBAL group id is always 64-bit.
+// rng_box_kernel (below) computes the same values for any number of
+// levels and serves every untailed window. Tailed windows keep this
+// kernel: it carries four geometry scalars next to the tail program where
+// the box kernel carries a four-level box, and the tailed box kernel's
+// SGPR pressure (7 waves per SIMD where this one has 8 on bf16) measured
+// 3-5 % slower on them (profiles/one_rng_kernel_family.md).
 template <typename T, Dist kDist, typename IdxT>
 __global__ void rng_chain_window_kernel(T* __restrict__ out,
                                         IdxT n_blocks,
@@ -1053,11 +908,38 @@ TailProgram makeTailProgram(at::IntArrayRef tail_ops,
   return prog;
 }
 
-template <Dist kDist>
-void launchRngChainWindow(at::Tensor& shard, int64_t n_blocks,
-                          int64_t block_len, int64_t g_stride, int64_t g_off,
-                          double p0, double p1, const TailProgram& prog,
-                          int64_t seed, int64_t offset) {
+// Calls f(std::integral_constant<Dist, ...>{}) for the ops' dist code —
+// 0 uniform, 1 normal, 2 bernoulli — after that distribution's parameter
+// check; `what` names the op in the error for any other code.
+template <typename F>
+void dispatchDist(int64_t dist, double p0, double p1, const char* what,
+                  F&& f) {
+  switch (dist) {
+    case 0:
+      f(std::integral_constant<Dist, Dist::kUniform>{});
+      break;
+    case 1:
+      TORCH_CHECK(p1 >= 0.0, "normal_ expects std >= 0.0, but found std=",
+                  p1);
+      f(std::integral_constant<Dist, Dist::kNormal>{});
+      break;
+    case 2:
+      TORCH_CHECK(0.0 <= p0 && p0 <= 1.0,
+                  "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
+      f(std::integral_constant<Dist, Dist::kBernoulli>{});
+      break;
+    default:
+      TORCH_CHECK(false, what, ": dist must be 0 (uniform), 1 (normal) or 2 "
+                               "(bernoulli), got ", dist);
+  }
+}
+
+// The argument checks of every op that takes one strided window: the
+// shard is n_blocks contiguous global ranges of block_len elements, block
+// r starting at global element g_off + r * g_stride
+// (`full.narrow(dim, s, len)` flattened).
+void checkShardWindow(const at::Tensor& shard, int64_t n_blocks,
+                      int64_t block_len, int64_t g_stride, int64_t g_off) {
   TORCH_CHECK(shard.is_contiguous(),
               "tdx shard kernels require contiguous tensors");
   TORCH_CHECK(n_blocks >= 0 && block_len >= 0 && g_stride >= block_len &&
@@ -1065,17 +947,26 @@ void launchRngChainWindow(at::Tensor& shard, int64_t n_blocks,
               "invalid shard window");
   TORCH_CHECK(shard.numel() == n_blocks * block_len,
               "shard numel must equal n_blocks * block_len");
-  if (shard.numel() == 0) {
-    return;
-  }
-  float a = static_cast<float>(p0);
-  float b = kDist == Dist::kUniform ? static_cast<float>(p1 - p0)
-                                    : static_cast<float>(p1);
+}
+
+void checkWindowFits(int64_t n_blocks, int64_t block_len, int64_t g_stride,
+                     int64_t g_off, int64_t full_numel) {
+  TORCH_CHECK(full_numel >= g_off + (n_blocks > 0 ? (n_blocks - 1) * g_stride
+                                                  + block_len : 0),
+              "rng_chain: the window does not fit in full_numel");
+}
+
+template <Dist kDist>
+void launchRngChainWindow(at::Tensor& shard, int64_t n_blocks,
+                          int64_t block_len, int64_t g_stride, int64_t g_off,
+                          double p0, double p1, const TailProgram& prog,
+                          int64_t seed, int64_t offset) {
+  const Affine ab = affineOf<kDist>(p0, p1);
   const bool vec_ok =
       reinterpret_cast<uintptr_t>(shard.data_ptr()) % 16 == 0;
   auto stream = at::cuda::getCurrentCUDAStream();
-  auto launch = [&](auto type_tag) {
-    using T = decltype(type_tag);
+  dispatchFloat3(shard.scalar_type(), "tdx shard kernels", [&](auto tag) {
+    using T = decltype(tag);
     const int64_t n_work =
         (shard.numel() + VecTraits<T>::kElems - 1) / VecTraits<T>::kElems;
     auto launch_idx = [&](auto idx_tag) {
@@ -1086,7 +977,7 @@ void launchRngChainWindow(at::Tensor& shard, int64_t n_blocks,
                          reinterpret_cast<T*>(shard.data_ptr()),
                          static_cast<IdxT>(n_blocks),
                          static_cast<IdxT>(block_len), g_stride, g_off,
-                         vec_ok, a, b, static_cast<uint64_t>(seed),
+                         vec_ok, ab.a, ab.b, static_cast<uint64_t>(seed),
                          static_cast<uint64_t>(offset), prog);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     };
@@ -1095,69 +986,7 @@ void launchRngChainWindow(at::Tensor& shard, int64_t n_blocks,
     } else {
       launch_idx(int64_t{});
     }
-  };
-  switch (shard.scalar_type()) {
-    case at::kFloat:
-      launch(float{});
-      break;
-    case at::kBFloat16:
-      launch(__hip_bfloat16{});
-      break;
-    case at::kHalf:
-      launch(__half{});
-      break;
-    default:
-      TORCH_CHECK(false, "tdx chain kernels support float32/bf16/fp16, got ",
-                  shard.scalar_type());
-  }
-}
-
-at::Tensor& tdx_rng_chain_shard_win_(
-    at::Tensor& shard, int64_t n_blocks, int64_t block_len, int64_t g_stride,
-    int64_t g_off, int64_t dist, double p0, double p1,
-    at::IntArrayRef tail_ops, at::ArrayRef<double> tail_s0,
-    at::ArrayRef<double> tail_s1, int64_t full_numel, int64_t seed,
-    int64_t offset) {
-  TORCH_CHECK(full_numel >= g_off + (n_blocks > 0 ? (n_blocks - 1) * g_stride
-                                                  + block_len : 0),
-              "rng_chain: the window does not fit in full_numel");
-  const TailProgram prog =
-      makeTailProgram(tail_ops, tail_s0, tail_s1, full_numel);
-  switch (dist) {
-    case 0:
-      launchRngChainWindow<Dist::kUniform>(shard, n_blocks, block_len,
-                                           g_stride, g_off, p0, p1, prog,
-                                           seed, offset);
-      break;
-    case 1:
-      TORCH_CHECK(p1 >= 0.0, "normal_ expects std >= 0.0, but found std=",
-                  p1);
-      launchRngChainWindow<Dist::kNormal>(shard, n_blocks, block_len,
-                                          g_stride, g_off, p0, p1, prog,
-                                          seed, offset);
-      break;
-    case 2:
-      TORCH_CHECK(0.0 <= p0 && p0 <= 1.0,
-                  "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
-      launchRngChainWindow<Dist::kBernoulli>(shard, n_blocks, block_len,
-                                             g_stride, g_off, p0, 0.0, prog,
-                                             seed, offset);
-      break;
-    default:
-      TORCH_CHECK(false, "rng_chain: dist must be 0 (uniform), 1 (normal) "
-                         "or 2 (bernoulli), got ", dist);
-  }
-  return shard;
-}
-
-at::Tensor& tdx_rng_chain_(at::Tensor& self, int64_t dist, double p0,
-                           double p1, at::IntArrayRef tail_ops,
-                           at::ArrayRef<double> tail_s0,
-                           at::ArrayRef<double> tail_s1, int64_t seed,
-                           int64_t offset) {
-  return tdx_rng_chain_shard_win_(self, 1, self.numel(), self.numel(), 0,
-                                  dist, p0, p1, tail_ops, tail_s0, tail_s1,
-                                  self.numel(), seed, offset);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1458,9 +1287,10 @@ void launchRngChainCastWindow(at::Tensor& shard, c10::ScalarType src_dtype,
                               int64_t g_stride, int64_t g_off, double p0,
                               double p1, const TailProgram& prog,
                               int64_t seed, int64_t offset) {
-  float a = static_cast<float>(p0);
-  float b = kDist == Dist::kUniform ? static_cast<float>(p1 - p0)
-                                    : static_cast<float>(p1);
+  if (shard.numel() == 0) {
+    return;
+  }
+  const Affine ab = affineOf<kDist>(p0, p1);
   const bool vec_ok =
       reinterpret_cast<uintptr_t>(shard.data_ptr()) % 16 == 0;
   auto stream = at::cuda::getCurrentCUDAStream();
@@ -1477,8 +1307,9 @@ void launchRngChainCastWindow(at::Tensor& shard, c10::ScalarType src_dtype,
               dim3(numBlocks(n_work)), dim3(kBlock), 0, stream.stream(),
               reinterpret_cast<TDst*>(shard.data_ptr()),
               static_cast<IdxT>(n_blocks), static_cast<IdxT>(block_len),
-              g_stride, g_off, vec_ok, a, b, static_cast<uint64_t>(seed),
-              static_cast<uint64_t>(offset), prog);
+              g_stride, g_off, vec_ok, ab.a, ab.b,
+              static_cast<uint64_t>(seed), static_cast<uint64_t>(offset),
+              prog);
           C10_HIP_KERNEL_LAUNCH_CHECK();
         };
         if (shard.numel() <= std::numeric_limits<int32_t>::max()) {
@@ -1500,45 +1331,15 @@ at::Tensor& tdx_rng_chain_cast_shard_win_(
                   src_dtype != shard.scalar_type(),
               "rng_chain_cast: two different dtypes of float32/bf16/fp16, "
               "got ", src_dtype, " -> ", shard.scalar_type());
-  TORCH_CHECK(shard.is_contiguous(),
-              "tdx shard kernels require contiguous tensors");
-  TORCH_CHECK(n_blocks >= 0 && block_len >= 0 && g_stride >= block_len &&
-                  g_off >= 0,
-              "invalid shard window");
-  TORCH_CHECK(shard.numel() == n_blocks * block_len,
-              "shard numel must equal n_blocks * block_len");
-  TORCH_CHECK(full_numel >= g_off + (n_blocks > 0 ? (n_blocks - 1) * g_stride
-                                                  + block_len : 0),
-              "rng_chain: the window does not fit in full_numel");
+  checkShardWindow(shard, n_blocks, block_len, g_stride, g_off);
+  checkWindowFits(n_blocks, block_len, g_stride, g_off, full_numel);
   const TailProgram prog =
       makeTailProgram(tail_ops, tail_s0, tail_s1, full_numel);
-  TORCH_CHECK(0 <= dist && dist <= 2,
-              "rng_chain: dist must be 0 (uniform), 1 (normal) or 2 "
-              "(bernoulli), got ", dist);
-  TORCH_CHECK(dist != 1 || p1 >= 0.0,
-              "normal_ expects std >= 0.0, but found std=", p1);
-  TORCH_CHECK(dist != 2 || (0.0 <= p0 && p0 <= 1.0),
-              "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
-  if (shard.numel() == 0) {
-    return shard;
-  }
-  switch (dist) {
-    case 0:
-      launchRngChainCastWindow<Dist::kUniform>(shard, src_dtype, n_blocks,
-                                               block_len, g_stride, g_off,
-                                               p0, p1, prog, seed, offset);
-      break;
-    case 1:
-      launchRngChainCastWindow<Dist::kNormal>(shard, src_dtype, n_blocks,
-                                              block_len, g_stride, g_off, p0,
-                                              p1, prog, seed, offset);
-      break;
-    default:
-      launchRngChainCastWindow<Dist::kBernoulli>(shard, src_dtype, n_blocks,
-                                                 block_len, g_stride, g_off,
-                                                 p0, 0.0, prog, seed, offset);
-      break;
-  }
+  dispatchDist(dist, p0, p1, "rng_chain", [&](auto d) {
+    launchRngChainCastWindow<decltype(d)::value>(
+        shard, src_dtype, n_blocks, block_len, g_stride, g_off, p0, p1, prog,
+        seed, offset);
+  });
   return shard;
 }
 
@@ -1556,20 +1357,25 @@ at::Tensor& tdx_rng_chain_cast_(at::Tensor& self, at::ScalarType src_dtype,
 
 // ---------------------------------------------------------------------------
 // N-d box kernel: materializes full[lo_0:hi_0, ..., lo_{r-1}:hi_{r-1}] of a
-// contiguous virtual full tensor. The box arrives normalized (BoxGeometry
-// in csrc/core/box_geometry.h): equally long contiguous runs nested under
-// up to kMaxBoxLevels strided levels — rng_chain_window_kernel's geometry
-// with more than one level. A shard unit (a 16-byte group on the vector
-// path, an element otherwise) splits into its run and its place within
-// the run; the run index is decomposed innermost level first, and every
-// coordinate adds its level's stride to the GLOBAL unit index. From there
-// on the value is computed exactly as in the kernels above (same group
-// id, lane, from_float barrier and tail), so a box is bitwise a sub-tensor
-// of the full materialization.
-// The decomposition costs one division per level. On the 32-bit index
-// path those are multiply-shift divisions by host-computed magics
-// (MagicDiv32); the 64-bit path (shards of 2^31 elements or more) divides
-// plainly.
+// contiguous virtual full tensor, with or without a fused tail. The box
+// arrives normalized (BoxGeometry in csrc/core/box_geometry.h): equally
+// long contiguous runs nested under up to kMaxBoxLevels strided levels.
+// One level is the window of a single-dim slice
+// (`full.narrow(dim, s, len)`: extent runs of run_len elements, g_stride
+// apart): the untailed window ops and the box op below launch this kernel;
+// a tailed window stays on rng_chain_window_kernel (see there).
+// A shard unit (a 16-byte group on the vector path, an element otherwise)
+// splits into its run and its place within the run; the run index is
+// decomposed innermost level first, and every coordinate adds its level's
+// stride to the GLOBAL unit index. The value of global element g is lane
+// g % kElems of Philox group g / kElems, computed exactly as in the
+// kernels above (same group id, lane, from_float barrier and tail), so a
+// box is bitwise a sub-tensor of the full materialization.
+// The decomposition costs one division per level. IdxT is the SHARD-side
+// index type: 32-bit below 2^31 shard elements, where the divisions are
+// multiply-shift divisions by host-computed magics (MagicDiv32); the
+// 64-bit path divides plainly. Only the GLOBAL unit index is always
+// 64-bit, built with multiplies.
 // ---------------------------------------------------------------------------
 
 // Geometry in UNITS (groups on the vector path, elements otherwise).
@@ -1623,8 +1429,9 @@ __device__ __forceinline__ uint64_t boxGlobalUnit(const BoxArgs<IdxT>& box,
 // `vec`: the host's check that `out` is 16-byte aligned and that g_off,
 // run_len and every stride are group multiples — `box` is then in groups
 // and every group of the box is whole. `n_units` is the shard's group
-// (vec) or element count. kHasTail == false carries no tail code.
-template <typename T, Dist kDist, typename IdxT, bool kHasTail, bool kMagic>
+// (vec) or element count. kHasTail == false carries no tail code; the
+// 32-bit index path divides by multiply-shift.
+template <typename T, Dist kDist, typename IdxT, bool kHasTail>
 __global__ void rng_box_kernel(T* __restrict__ out,
                                BoxArgs<IdxT> box,
                                IdxT n_units,
@@ -1635,6 +1442,7 @@ __global__ void rng_box_kernel(T* __restrict__ out,
                                uint64_t offset,
                                TailProgram prog) {
   constexpr int kElems = VecTraits<T>::kElems;
+  constexpr bool kMagic = std::is_same_v<IdxT, uint32_t>;
   using Vec = typename VecTraits<T>::Vec;
   const IdxT stride = static_cast<IdxT>(gridDim.x) * blockDim.x;
   if (vec) {
@@ -1669,27 +1477,20 @@ __global__ void rng_box_kernel(T* __restrict__ out,
   }
 }
 
-// Benchmark switch (scripts/box_kernel_bench.py): with TDX_BOX_PLAIN_DIV=1
-// in the environment the untailed 32-bit normal kernels divide with `/`,
-// so one process can time both forms alternately.
-bool boxPlainDivRequested() {
-  const char* v = std::getenv("TDX_BOX_PLAIN_DIV");
-  return v != nullptr && v[0] == '1';
-}
-
 template <Dist kDist>
 void launchRngBox(at::Tensor& shard, const BoxGeometry& geo, double p0,
                   double p1, const TailProgram& prog, int64_t seed,
                   int64_t offset) {
-  float a = static_cast<float>(p0);
-  float b = kDist == Dist::kUniform ? static_cast<float>(p1 - p0)
-                                    : static_cast<float>(p1);
   const int64_t numel = shard.numel();
+  if (numel == 0) {
+    return;
+  }
+  const Affine ab = affineOf<kDist>(p0, p1);
   const bool ptr_ok = reinterpret_cast<uintptr_t>(shard.data_ptr()) % 16 == 0;
   const bool has_tail = prog.n > 0;
   auto stream = at::cuda::getCurrentCUDAStream();
-  auto launch = [&](auto type_tag) {
-    using T = decltype(type_tag);
+  dispatchFloat3(shard.scalar_type(), "tdx shard kernels", [&](auto tag) {
+    using T = decltype(tag);
     constexpr int64_t kElems = VecTraits<T>::kElems;
     bool vec = ptr_ok && geo.g_off % kElems == 0 && geo.run_len % kElems == 0;
     for (int l = 0; l < geo.levels; ++l) {
@@ -1698,10 +1499,9 @@ void launchRngBox(at::Tensor& shard, const BoxGeometry& geo, double p0,
     const int64_t unit = vec ? kElems : 1;
     const int64_t n_units = numel / unit;  // vec: numel is a group multiple
     const int64_t n_work = (numel + kElems - 1) / kElems;
-    auto launch_idx = [&](auto idx_tag, auto tail_tag, auto magic_tag) {
+    auto launch_idx = [&](auto idx_tag, auto tail_tag) {
       using IdxT = decltype(idx_tag);
       constexpr bool kHasTail = decltype(tail_tag)::value;
-      constexpr bool kMagic = decltype(magic_tag)::value;
       BoxArgs<IdxT> box{};
       box.g0 = static_cast<uint64_t>(geo.g_off / unit);
       box.run = static_cast<IdxT>(geo.run_len / unit);
@@ -1714,55 +1514,38 @@ void launchRngBox(at::Tensor& shard, const BoxGeometry& geo, double p0,
         box.gs[l] = static_cast<uint64_t>(geo.g_stride[l] / unit);
         box.ext[l] = static_cast<IdxT>(geo.extent[l]);
       }
-      if constexpr (kMagic) {
-        const MagicDiv32 rd = makeMagicDiv32(static_cast<uint32_t>(box.run));
+      if constexpr (std::is_same_v<IdxT, uint32_t>) {
+        const MagicDiv32 rd = makeMagicDiv32(box.run);
         box.run_magic = rd.magic;
         box.run_shift = rd.shift;
         for (int l = 1; l < kMaxBoxLevels; ++l) {
-          const MagicDiv32 ed =
-              makeMagicDiv32(static_cast<uint32_t>(box.ext[l]));
+          const MagicDiv32 ed = makeMagicDiv32(box.ext[l]);
           box.ext_magic[l - 1] = ed.magic;
           box.ext_shift[l - 1] = ed.shift;
         }
       }
       hipLaunchKernelGGL(
-          (rng_box_kernel<T, kDist, IdxT, kHasTail, kMagic>),
+          (rng_box_kernel<T, kDist, IdxT, kHasTail>),
           dim3(numBlocks(n_work)), dim3(kBlock), 0, stream.stream(),
           reinterpret_cast<T*>(shard.data_ptr()), box,
-          static_cast<IdxT>(n_units), vec, a, b,
+          static_cast<IdxT>(n_units), vec, ab.a, ab.b,
           static_cast<uint64_t>(seed), static_cast<uint64_t>(offset), prog);
       C10_HIP_KERNEL_LAUNCH_CHECK();
     };
-    if (numel > std::numeric_limits<int32_t>::max()) {
+    auto launch_tail = [&](auto idx_tag) {
       if (has_tail) {
-        launch_idx(int64_t{}, std::true_type{}, std::false_type{});
+        launch_idx(idx_tag, std::true_type{});
       } else {
-        launch_idx(int64_t{}, std::false_type{}, std::false_type{});
+        launch_idx(idx_tag, std::false_type{});
       }
-    } else if (has_tail) {
-      launch_idx(uint32_t{}, std::true_type{}, std::true_type{});
-    } else if (kDist == Dist::kNormal && boxPlainDivRequested()) {
-      if constexpr (kDist == Dist::kNormal) {
-        launch_idx(uint32_t{}, std::false_type{}, std::false_type{});
-      }
+    };
+    // The multiply-shift division is exact below 2^31.
+    if (numel > std::numeric_limits<int32_t>::max()) {
+      launch_tail(int64_t{});
     } else {
-      launch_idx(uint32_t{}, std::false_type{}, std::true_type{});
+      launch_tail(uint32_t{});
     }
-  };
-  switch (shard.scalar_type()) {
-    case at::kFloat:
-      launch(float{});
-      break;
-    case at::kBFloat16:
-      launch(__hip_bfloat16{});
-      break;
-    case at::kHalf:
-      launch(__half{});
-      break;
-    default:
-      TORCH_CHECK(false, "tdx box kernel supports float32/bf16/fp16, got ",
-                  shard.scalar_type());
-  }
+  });
 }
 
 at::Tensor& tdx_rng_box_(at::Tensor& shard, at::IntArrayRef extents,
@@ -1781,42 +1564,87 @@ at::Tensor& tdx_rng_box_(at::Tensor& shard, at::IntArrayRef extents,
   TORCH_CHECK(err == nullptr, "rng_box: ", err);
   const TailProgram prog =
       makeTailProgram(tail_ops, tail_s0, tail_s1, full_numel);
-  TORCH_CHECK(dist != 1 || p1 >= 0.0,
-              "normal_ expects std >= 0.0, but found std=", p1);
-  TORCH_CHECK(dist != 2 || (0.0 <= p0 && p0 <= 1.0),
-              "bernoulli_ expects 0 <= p <= 1, but found p=", p0);
-  TORCH_CHECK(0 <= dist && dist <= 2,
-              "rng_box: dist must be 0 (uniform), 1 (normal) or 2 "
-              "(bernoulli), got ", dist);
   TORCH_CHECK(shard.scalar_type() == at::kFloat ||
                   shard.scalar_type() == at::kBFloat16 ||
                   shard.scalar_type() == at::kHalf,
               "tdx box kernel supports float32/bf16/fp16, got ",
               shard.scalar_type());
-  if (shard.numel() == 0) {
-    return shard;
-  }
-  BoxGeometry geo;
-  geo.g_off = g_off;
-  geo.run_len = run_len;
-  geo.levels = static_cast<int32_t>(extents.size());
-  for (int l = 0; l < geo.levels; ++l) {
-    geo.extent[l] = extents[l];
-    geo.g_stride[l] = g_strides[l];
-  }
-  switch (dist) {
-    case 0:
-      launchRngBox<Dist::kUniform>(shard, geo, p0, p1, prog, seed, offset);
-      break;
-    case 1:
-      launchRngBox<Dist::kNormal>(shard, geo, p0, p1, prog, seed, offset);
-      break;
-    default:
-      launchRngBox<Dist::kBernoulli>(shard, geo, p0, 0.0, prog, seed,
-                                     offset);
-      break;
-  }
+  const BoxGeometry geo = boxFromArgs(extents.data(), g_strides.data(),
+                                      extents.size(), run_len, g_off);
+  dispatchDist(dist, p0, p1, "rng_box", [&](auto d) {
+    launchRngBox<decltype(d)::value>(shard, geo, p0, p1, prog, seed, offset);
+  });
   return shard;
+}
+
+// The untailed single-dim window ops: one strided level (checkShardWindow
+// has the geometry) on the box kernel. `dist` as in dispatchDist.
+at::Tensor& rngShardWindow(at::Tensor& shard, int64_t n_blocks,
+                           int64_t block_len, int64_t g_stride,
+                           int64_t g_off, int64_t dist, double p0, double p1,
+                           int64_t seed, int64_t offset) {
+  dispatchDist(dist, p0, p1, "shard_win", [&](auto d) {
+    checkShardWindow(shard, n_blocks, block_len, g_stride, g_off);
+    launchRngBox<decltype(d)::value>(
+        shard, boxFromArgs(&n_blocks, &g_stride, 1, block_len, g_off), p0, p1,
+        TailProgram{}, seed, offset);
+  });
+  return shard;
+}
+
+at::Tensor& tdx_uniform_shard_win_(at::Tensor& shard, int64_t n_blocks,
+                                   int64_t block_len, int64_t g_stride,
+                                   int64_t g_off, double from, double to,
+                                   int64_t seed, int64_t offset) {
+  return rngShardWindow(shard, n_blocks, block_len, g_stride, g_off, 0, from,
+                        to, seed, offset);
+}
+
+at::Tensor& tdx_normal_shard_win_(at::Tensor& shard, int64_t n_blocks,
+                                  int64_t block_len, int64_t g_stride,
+                                  int64_t g_off, double mean, double std,
+                                  int64_t seed, int64_t offset) {
+  return rngShardWindow(shard, n_blocks, block_len, g_stride, g_off, 1, mean,
+                        std, seed, offset);
+}
+
+at::Tensor& tdx_bernoulli_shard_win_(at::Tensor& shard, int64_t n_blocks,
+                                     int64_t block_len, int64_t g_stride,
+                                     int64_t g_off, double p, int64_t seed,
+                                     int64_t offset) {
+  return rngShardWindow(shard, n_blocks, block_len, g_stride, g_off, 2, p,
+                        0.0, seed, offset);
+}
+
+// The tailed window op, on the chain window kernel (see there for why).
+at::Tensor& tdx_rng_chain_shard_win_(
+    at::Tensor& shard, int64_t n_blocks, int64_t block_len, int64_t g_stride,
+    int64_t g_off, int64_t dist, double p0, double p1,
+    at::IntArrayRef tail_ops, at::ArrayRef<double> tail_s0,
+    at::ArrayRef<double> tail_s1, int64_t full_numel, int64_t seed,
+    int64_t offset) {
+  checkWindowFits(n_blocks, block_len, g_stride, g_off, full_numel);
+  const TailProgram prog =
+      makeTailProgram(tail_ops, tail_s0, tail_s1, full_numel);
+  dispatchDist(dist, p0, p1, "rng_chain", [&](auto d) {
+    checkShardWindow(shard, n_blocks, block_len, g_stride, g_off);
+    if (shard.numel() != 0) {
+      launchRngChainWindow<decltype(d)::value>(shard, n_blocks, block_len,
+                                               g_stride, g_off, p0, p1, prog,
+                                               seed, offset);
+    }
+  });
+  return shard;
+}
+
+at::Tensor& tdx_rng_chain_(at::Tensor& self, int64_t dist, double p0,
+                           double p1, at::IntArrayRef tail_ops,
+                           at::ArrayRef<double> tail_s0,
+                           at::ArrayRef<double> tail_s1, int64_t seed,
+                           int64_t offset) {
+  return tdx_rng_chain_shard_win_(self, 1, self.numel(), self.numel(), 0,
+                                  dist, p0, p1, tail_ops, tail_s0, tail_s1,
+                                  self.numel(), seed, offset);
 }
 
 // ---------------------------------------------------------------------------
@@ -2042,14 +1870,8 @@ at::Tensor& tdx_patch_box_(at::Tensor& shard, at::IntArrayRef extents,
                   shard.scalar_type() == at::kHalf,
               "tdx patch kernel supports float32/bf16/fp16, got ",
               shard.scalar_type());
-  BoxGeometry geo;
-  geo.g_off = g_off;
-  geo.run_len = run_len;
-  geo.levels = static_cast<int32_t>(extents.size());
-  for (int l = 0; l < geo.levels; ++l) {
-    geo.extent[l] = extents[l];
-    geo.g_stride[l] = g_strides[l];
-  }
+  const BoxGeometry geo = boxFromArgs(extents.data(), g_strides.data(),
+                                      extents.size(), run_len, g_off);
   const RowRange rows = rowsMeeting(geo, patch_lo, patch_lo + patch_len);
   if (rows.count() == 0) {
     return shard;  // the patch misses the box (or one of them is empty)
