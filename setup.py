@@ -55,6 +55,7 @@ hip_sources = [
     os.path.join(CSRC, "hip", "init_kernels.hip"),
     os.path.join(CSRC, "hip", "anyprecision_adamw.hip"),
     os.path.join(CSRC, "hip", "anyprecision_adamw_q8.hip"),
+    os.path.join(CSRC, "hip", "anyprecision_adamw_resident.hip"),
     os.path.join(CSRC, "hip", "grad_norm.hip"),
     os.path.join(CSRC, "hip", "slowmo.hip"),
     os.path.join(CSRC, "hip", "kernels_module.cc"),

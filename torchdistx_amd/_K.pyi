@@ -1,6 +1,6 @@
 # Typing stub for the CDNA4 kernel extension.
 
-from typing import List, Optional, Tuple
+from typing import List, Optional, Tuple, Union
 
 import torch
 
@@ -64,6 +64,39 @@ def anyprecision_adamw_q8_(
     ordinals: Optional[List[int]] = None,
     steps: Optional[List[int]] = None,
 ) -> None: ...
+def has_anyprecision_adamw_resident() -> bool: ...
+
+class AdamWResidentPlan:
+    def __init__(
+        self,
+        params: List[torch.Tensor],
+        grads: List[torch.Tensor],
+        exp_avgs: List[torch.Tensor],
+        exp_avg_scales: List[Optional[torch.Tensor]],
+        exp_avg_sqs: List[torch.Tensor],
+        exp_avg_sq_scales: List[Optional[torch.Tensor]],
+        compensations: List[Optional[torch.Tensor]],
+        steps: List[torch.Tensor],
+        ordinals: List[int],
+    ) -> None: ...
+    def matches(self, grads: List[torch.Tensor]) -> bool: ...
+    def stale(self) -> bool: ...
+    def rebind(self, grads: List[torch.Tensor]) -> None: ...
+    def step(
+        self,
+        lr: Union[float, torch.Tensor],
+        beta1: float,
+        beta2: float,
+        eps: float,
+        weight_decay: float,
+        grad_scale: Optional[torch.Tensor] = None,
+        sr_seed: Optional[int] = None,
+    ) -> None: ...
+    def scalars(
+        self,
+    ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]: ...
+    def __len__(self) -> int: ...
+
 def grad_norm_clip_coef_(
     grads: List[torch.Tensor],
     max_norm: float,

@@ -150,6 +150,28 @@ def anyprecision_adamw_q8_(
     )
 
 
+def has_anyprecision_adamw_resident() -> bool:
+    return (
+        _HAS_K
+        and torch.cuda.is_available()
+        and hasattr(_K, "has_anyprecision_adamw_resident")
+    )
+
+
+def adamw_resident_plan(params, grads, exp_avgs, exp_avg_scales, exp_avg_sqs,
+                        exp_avg_sq_scales, compensations, steps, ordinals):
+    """The device-resident launch plan (_K.AdamWResidentPlan; see
+    csrc/hip/anyprecision_adamw_resident.hip) of one capturable param group:
+    the lists of anyprecision_adamw_q8_, with each tensor's state["step"] (a
+    0-dim float32 device tensor) and its index over all param groups in
+    place of the host-formed scalars. Validates and uploads once; the plan's
+    step(lr, beta1, beta2, eps, weight_decay, grad_scale, sr_seed) is then
+    two kernel launches and can be captured in a HIP graph."""
+    return _K.AdamWResidentPlan(
+        params, grads, exp_avgs, exp_avg_scales, exp_avg_sqs,
+        exp_avg_sq_scales, compensations, steps, ordinals)
+
+
 def has_grad_norm() -> bool:
     return (
         _HAS_K

@@ -5,6 +5,10 @@
 
 #include <torch/extension.h>
 
+#include <variant>
+
+#include "adamw_resident_plan.h"
+
 namespace tdx {
 
 void anyprecision_adamw_step(at::Tensor& param,
@@ -95,6 +99,7 @@ PYBIND11_MODULE(_K, m) {
   m.def("has_anyprecision_adamw", [] { return true; });
   m.def("has_anyprecision_adamw_batched", [] { return true; });
   m.def("has_anyprecision_adamw_q8", [] { return true; });
+  m.def("has_anyprecision_adamw_resident", [] { return true; });
   m.def("has_grad_norm", [] { return true; });
   m.def("has_slowmo", [] { return true; });
   m.def("has_batched_init", [] { return true; });
@@ -153,6 +158,60 @@ PYBIND11_MODULE(_K, m) {
         "With sr_seed, bf16 parameters are stored with stochastic rounding: "
         "Philox4x32-10 keyed by sr_seed, per tensor the subsequence "
         "(steps[t] << 32) | ordinals[t].");
+
+  pybind11::class_<tdx::AdamWResidentPlan>(
+      m, "AdamWResidentPlan",
+      "Device-resident launch plan of one capturable AnyPrecisionAdamW "
+      "param group: the multi-tensor table of anyprecision_adamw_q8_ built, "
+      "validated and uploaded once, with each tensor's state['step'] (a "
+      "1-element float32 device tensor) in place of the scalars the host "
+      "bakes in per call. step() is two launches and can be captured in a "
+      "HIP graph.")
+      .def(pybind11::init<
+               std::vector<at::Tensor>, std::vector<at::Tensor>,
+               std::vector<at::Tensor>, std::vector<std::optional<at::Tensor>>,
+               std::vector<at::Tensor>, std::vector<std::optional<at::Tensor>>,
+               std::vector<std::optional<at::Tensor>>, std::vector<at::Tensor>,
+               std::vector<int64_t>>(),
+           pybind11::arg("params"), pybind11::arg("grads"),
+           pybind11::arg("exp_avgs"), pybind11::arg("exp_avg_scales"),
+           pybind11::arg("exp_avg_sqs"), pybind11::arg("exp_avg_sq_scales"),
+           pybind11::arg("compensations"), pybind11::arg("steps"),
+           pybind11::arg("ordinals"))
+      .def("matches", &tdx::AdamWResidentPlan::matches, pybind11::arg("grads"),
+           "Whether these are the gradients the table points at (pointer "
+           "comparison only).")
+      .def("stale", &tdx::AdamWResidentPlan::stale,
+           "Whether a parameter or state tensor of the plan has moved or "
+           "changed size: build a new plan.")
+      .def("rebind", &tdx::AdamWResidentPlan::rebind, pybind11::arg("grads"),
+           "Point the table at new gradients of the same tensors and upload "
+           "it again.")
+      .def(
+          "step",
+          [](tdx::AdamWResidentPlan& plan,
+             std::variant<double, at::Tensor> lr, double beta1, double beta2,
+             double eps, double weight_decay,
+             std::optional<at::Tensor> grad_scale,
+             std::optional<int64_t> sr_seed) {
+            const bool as_tensor = std::holds_alternative<at::Tensor>(lr);
+            plan.step(as_tensor ? 0.0 : std::get<double>(lr),
+                      as_tensor ? std::optional<at::Tensor>(
+                                      std::get<at::Tensor>(lr))
+                                : std::nullopt,
+                      beta1, beta2, eps, weight_decay, grad_scale, sr_seed);
+          },
+          pybind11::arg("lr"), pybind11::arg("beta1"), pybind11::arg("beta2"),
+          pybind11::arg("eps"), pybind11::arg("weight_decay"),
+          pybind11::arg("grad_scale") = pybind11::none(),
+          pybind11::arg("sr_seed") = pybind11::none(),
+          "One optimizer step on the current stream: the advance kernel "
+          "(step += 1, bias corrections and decay from lr, a float or a "
+          "1-element float32 device tensor), then the multi-tensor update.")
+      .def("scalars", &tdx::AdamWResidentPlan::scalars,
+           "Host copies (step_size, bias_correction2_sqrt, step, decay) of "
+           "the scalar slots as the last step left them; synchronizes.")
+      .def("__len__", &tdx::AdamWResidentPlan::size);
 
   m.def(
       "anyprecision_adamw_",

@@ -114,6 +114,21 @@ def _q8_kernel_loaded() -> bool:
         return False
 
 
+def _resident_kernel_loaded() -> bool:
+    try:
+        from torchdistx_amd import _kernels
+
+        return _kernels.has_anyprecision_adamw_resident()
+    except Exception:
+        return False
+
+
+_CAPTURE_WARM_UP = (
+    "run one eager step first and keep gradients in place, "
+    "`zero_grad(set_to_none=False)`"
+)
+
+
 def _grad_norm_kernel_loaded() -> bool:
     try:
         from torchdistx_amd import _kernels
@@ -228,6 +243,21 @@ class AnyPrecisionAdamW(Optimizer):
             same seed on every rank — pass it explicitly or seed the ranks
             identically — and then stay bitwise in sync. The seed is part
             of ``state_dict()["param_groups"]``.
+        capturable: make ``step`` safe to capture in a HIP graph
+            (``torch.cuda.graph``) (default: False). ``state["step"]`` is
+            then a 0-dim fp32 tensor on the parameter's device, ``lr`` may
+            be a 1-element fp32 tensor on that device (change it in place
+            for a schedule), and a step is two kernel launches from a
+            device-resident plan kept per param group, with no per-tensor
+            host work: one kernel advances the step counts and forms the
+            bias corrections on the device, the multi-tensor kernel applies
+            the update. Composes with Kahan summation, fp8 states,
+            stochastic rounding and, outside capture, ``max_grad_norm``.
+            Exists on the fused GPU path only — ``step`` raises
+            ``RuntimeError`` where that path cannot run. Run one eager step
+            before capturing and keep the gradient tensors in place
+            (``zero_grad(set_to_none=False)``): see
+            docs/anyprecision_adamw.md, "Graph capture".
     """
 
     def __init__(
@@ -245,6 +275,7 @@ class AnyPrecisionAdamW(Optimizer):
         max_grad_norm=None,
         stochastic_rounding=False,
         stochastic_rounding_seed=None,
+        capturable=False,
     ):
         if max_grad_norm is not None and (
                 isinstance(max_grad_norm, bool)
@@ -264,6 +295,7 @@ class AnyPrecisionAdamW(Optimizer):
             compensation_buffer_dtype=compensation_buffer_dtype,
             stochastic_rounding=stochastic_rounding,
             stochastic_rounding_seed=stochastic_rounding_seed,
+            capturable=capturable,
         )
         _check_state_dtypes(
             momentum_dtype, variance_dtype, compensation_buffer_dtype
@@ -303,6 +335,10 @@ class AnyPrecisionAdamW(Optimizer):
         # Views of the [norm, coef] tensor of the last step.
         self.grad_norm = None
         self.grad_clip_coef = None
+        # capturable=True: per index of a param group, the parameters that
+        # had gradients when its device-resident plan was built, and the
+        # plan (_K.AdamWResidentPlan).
+        self._resident_plans = {}
 
     def load_state_dict(self, state_dict):
         """Base-class restore, then re-cast the optimizer states to their
@@ -311,6 +347,8 @@ class AnyPrecisionAdamW(Optimizer):
         silently destroy the any-precision state layout (e.g. a bf16
         compensation buffer next to fp32 weights)."""
         super().load_state_dict(state_dict)
+        # The resident plans point at the state tensors replaced here.
+        self._resident_plans.clear()
         for group in self.param_groups:
             for p in group["params"]:
                 state = self.state.get(p)
@@ -376,6 +414,137 @@ class AnyPrecisionAdamW(Optimizer):
                 f"{what} the fused AnyPrecisionAdamW step, but {reason}"
             )
 
+    def _check_capturable_can_run(self, p, grad):
+        """capturable=True exists on the fused path only (the eager op
+        sequence keeps its step count on the host): name why it cannot
+        run. fp8 states and stochastic rounding have refused DTensors
+        before this is called."""
+        tensors = [_local_view(p), _local_view(grad)]
+        reason = None
+        if p.device.type != "cuda":
+            reason = f"the parameter is on {p.device.type}, not on a GPU"
+        elif not _resident_kernel_loaded():
+            reason = ("the kernel extension torchdistx_amd._K (with "
+                      "AdamWResidentPlan) is not loaded")
+        elif any(torch.utils._python_dispatch.is_traceable_wrapper_subclass(t)
+                 for t in tensors):
+            reason = ("the parameter or its gradient is a storage-less "
+                      "wrapper subclass")
+        elif grad.is_sparse:
+            reason = "the gradient is sparse"
+        elif not all(t.is_contiguous() for t in tensors):
+            reason = "the parameter or its gradient is non-contiguous"
+        if reason is not None:
+            raise RuntimeError(
+                "capturable=True needs the fused AnyPrecisionAdamW step, "
+                f"but {reason}"
+            )
+
+    def _build_resident_plan(self, group, with_grad, first_ordinal):
+        """State of the parameters that have none yet, the refusals, and
+        the group's _K.AdamWResidentPlan."""
+        from torchdistx_amd import _kernels
+
+        momentum_dtype = group["momentum_dtype"]
+        variance_dtype = group["variance_dtype"]
+        sr = group.get("stochastic_rounding", False)
+        q8 = (sr or momentum_dtype in _Q8_DTYPES
+              or variance_dtype in _Q8_DTYPES)
+        if sr:
+            _check_stochastic_rounding(group)
+        ordinal_of = {id(p): first_ordinal + i
+                      for i, p in enumerate(group["params"])}
+        cols = [[] for _ in range(9)]
+        for p in with_grad:
+            if q8:
+                self._check_q8_can_run(p, _q8_kernel_loaded(), sr)
+            self._check_capturable_can_run(p, p.grad)
+            if sr and p.dtype == torch.float16:
+                raise ValueError(
+                    "stochastic_rounding=True stores bfloat16 "
+                    "parameters (float32 ones as they are); a float16 "
+                    "parameter is not supported"
+                )
+            state = self.state[p]
+            if len(state) == 0:
+                state["step"] = torch.zeros(
+                    (), dtype=torch.float32, device=p.device)
+                state["exp_avg"] = torch.zeros_like(p, dtype=momentum_dtype)
+                state["exp_avg_sq"] = torch.zeros_like(
+                    p, dtype=variance_dtype)
+                if group["use_kahan_summation"]:
+                    state["compensation"] = torch.zeros_like(
+                        p, dtype=group["compensation_buffer_dtype"])
+                if momentum_dtype in _Q8_DTYPES:
+                    state["exp_avg_scale"] = _q8_scale(state["exp_avg"])
+                if variance_dtype in _Q8_DTYPES:
+                    state["exp_avg_sq_scale"] = _q8_scale(
+                        state["exp_avg_sq"])
+            row = (p, p.grad, state["exp_avg"], state.get("exp_avg_scale"),
+                   state["exp_avg_sq"], state.get("exp_avg_sq_scale"),
+                   state.get("compensation") if group["use_kahan_summation"]
+                   else None, state["step"])
+            for col, t in zip(cols, row):
+                col.append(_local_view(t))
+            cols[8].append(ordinal_of[id(p)])
+        return _kernels.adamw_resident_plan(*cols)
+
+    def _capturable_group_step(self, index, group, first_ordinal, clip_on):
+        """One step of a capturable=True group: gather the gradients, check
+        them against the group's resident plan, launch it. clip_on(device)
+        is the clip coefficient there, or None."""
+        if self.use_fused is False:
+            raise RuntimeError(
+                "capturable=True needs the fused AnyPrecisionAdamW step, "
+                "but use_fused=False forbids the fused step"
+            )
+        with_grad = [p for p in group["params"] if p.grad is not None]
+        if not with_grad:
+            return
+        # Before the plan and the states: a refused step leaves nothing.
+        lr = group["lr"]
+        if isinstance(lr, torch.Tensor) and (
+                lr.device != with_grad[0].device
+                or lr.dtype != torch.float32 or lr.numel() != 1):
+            raise RuntimeError(
+                "capturable=True takes lr as a Python float or a 1-element "
+                f"float32 tensor on the parameters' device, not {lr.dtype} "
+                f"with {lr.numel()} elements on {lr.device}"
+            )
+        kept, plan, unwrap = self._resident_plans.get(
+            index, (None, None, False))
+        grads = [p.grad for p in with_grad]
+        if unwrap:
+            grads = [_local_view(g) for g in grads]
+        same = (plan is not None and len(kept) == len(with_grad)
+                and all(a is b for a, b in zip(kept, with_grad))
+                and not plan.stale())
+        if not (same and plan.matches(grads)):
+            # The first GPU query of the step: CPU parameters are refused
+            # without one.
+            if with_grad[0].device.type == "cuda" and \
+                    torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(
+                    "capturable=True: the step's device-resident plan would "
+                    "have to be " + ("rebound to new gradient tensors"
+                                     if same else "built")
+                    + f" while the stream is capturing; {_CAPTURE_WARM_UP}"
+                )
+            if same:
+                plan.rebind(grads)
+            else:
+                plan = self._build_resident_plan(
+                    group, with_grad, first_ordinal)
+                unwrap = any(_is_dtensor(p) for p in with_grad)
+                self._resident_plans[index] = (with_grad, plan, unwrap)
+        beta1, beta2 = group["betas"]
+        plan.step(
+            lr, beta1, beta2, group["eps"], group["weight_decay"],
+            clip_on(grads[0].device),
+            group["stochastic_rounding_seed"]
+            if group.get("stochastic_rounding", False) else None)
+        self._fused_steps += len(with_grad)
+
     def _clip_norm_and_coef(self):
         """The 2-element fp32 tensor [norm, coef] of this step's gradients:
         their global L2 norm and the coefficient of ``clip_grad_norm_``,
@@ -429,6 +598,15 @@ class AnyPrecisionAdamW(Optimizer):
 
         clip = None  # the coefficient as a 1-element tensor, per device
         if self.max_grad_norm is not None:
+            if (any(g.get("capturable", False) for g in self.param_groups)
+                    and torch.cuda.is_available()
+                    and torch.cuda.is_current_stream_capturing()):
+                raise RuntimeError(
+                    "max_grad_norm cannot be captured in a graph yet: the "
+                    "gradient norm kernel builds its tensor table per call. "
+                    "Clip outside the captured region, or capture without "
+                    "max_grad_norm"
+                )
             norm_coef = self._clip_norm_and_coef()
             self.grad_norm, self.grad_clip_coef = norm_coef[0], norm_coef[1]
             clip = {norm_coef.device: norm_coef[1:2]}
@@ -441,7 +619,12 @@ class AnyPrecisionAdamW(Optimizer):
             return clip[device]
 
         ordinal = -1  # of a parameter over all groups, as state_dict counts
-        for group in self.param_groups:
+        for index, group in enumerate(self.param_groups):
+            if group.get("capturable", False):
+                self._capturable_group_step(
+                    index, group, ordinal + 1, clip_on)
+                ordinal += len(group["params"])
+                continue
             beta1, beta2 = group["betas"]
             lr = group["lr"]
             weight_decay = group["weight_decay"]
