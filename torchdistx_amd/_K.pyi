@@ -91,7 +91,10 @@ class AdamWResidentPlan:
         weight_decay: float,
         grad_scale: Optional[torch.Tensor] = None,
         sr_seed: Optional[int] = None,
+        found_inf: Optional[torch.Tensor] = None,
     ) -> None: ...
+    def grad_grid(self) -> int: ...
+    def grad_sumsq(self, partials: torch.Tensor, offset: int) -> None: ...
     def scalars(
         self,
     ) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]: ...
@@ -100,6 +103,14 @@ class AdamWResidentPlan:
 def grad_norm_clip_coef_(
     grads: List[torch.Tensor],
     max_norm: float,
+    out: torch.Tensor,
+) -> None: ...
+def grad_norm_finalize_resident_(
+    partials: Optional[torch.Tensor],
+    n_partials: int,
+    max_norm: Optional[float],
+    loss_scale: Optional[torch.Tensor],
+    found_inf: Optional[torch.Tensor],
     out: torch.Tensor,
 ) -> None: ...
 def grad_norm_grid_cap() -> int: ...

@@ -165,8 +165,10 @@ def adamw_resident_plan(params, grads, exp_avgs, exp_avg_scales, exp_avg_sqs,
     the lists of anyprecision_adamw_q8_, with each tensor's state["step"] (a
     0-dim float32 device tensor) and its index over all param groups in
     place of the host-formed scalars. Validates and uploads once; the plan's
-    step(lr, beta1, beta2, eps, weight_decay, grad_scale, sr_seed) is then
-    two kernel launches and can be captured in a HIP graph."""
+    step(lr, beta1, beta2, eps, weight_decay, grad_scale, sr_seed,
+    found_inf) is then two kernel launches and can be captured in a HIP
+    graph, and so can its grad_sumsq(partials, offset), the norm pass over
+    the same table (see grad_norm_finalize_resident_)."""
     return _K.AdamWResidentPlan(
         params, grads, exp_avgs, exp_avg_scales, exp_avg_sqs,
         exp_avg_sq_scales, compensations, steps, ordinals)
@@ -187,6 +189,21 @@ def grad_norm_clip_coef_(grads, max_norm, out):
     tensor on the gradients' device; nothing returns to the host. The step
     wrappers above take out[1:2] as grad_scale."""
     _K.grad_norm_clip_coef_(grads, max_norm, out)
+
+
+def grad_norm_finalize_resident_(partials, n_partials, max_norm, loss_scale,
+                                 found_inf, out):
+    """One workgroup adding partials[:n_partials], the fp64 sums of squares
+    the resident plans' grad_sumsq left, into out = [norm, coef, grad_mult,
+    found_inf] (4-element float32 on the gradients' device; see
+    csrc/hip/grad_norm.hip): the norm of the gradients divided by
+    loss_scale, the clip_grad_norm_ coefficient for max_norm (exactly 1 for
+    None), coef / loss_scale, and 1 where found_inf is not zero. loss_scale
+    and found_inf are 1-element float32 tensors on that device or None.
+    AdamWResidentPlan.step takes out[2:3] as grad_scale and out[3:4] as
+    found_inf."""
+    _K.grad_norm_finalize_resident_(partials, n_partials, max_norm,
+                                    loss_scale, found_inf, out)
 
 
 def has_slowmo() -> bool:

@@ -53,6 +53,9 @@ struct Q8Header {
   float one_minus_beta1, one_minus_beta2, decay;  // host-narrowed
   const float* grad_scale;  // nullptr, or one fp32 every gradient is scaled by
   uint64_t sr_seed;         // Philox key of the stochastic rounding
+  // Resident steps under a GradScaler only, else nullptr: one fp32 that,
+  // when it is not zero, makes the whole step leave everything as it is.
+  const float* found_inf;
 };
 
 // What the host bakes into Q8TensorMeta and Q8Header per call, formed on
@@ -86,8 +89,27 @@ Q8TensorMeta checkedQ8TensorMeta(const at::Tensor& param,
 
 // Launches the kResident instantiation of adamw_q8_kernel over a resident
 // table on `stream`. h.decay is ignored (the table's decay slot is read).
+// With h.found_inf the kSkip instantiation, which reads it first.
 void launchAdamwQ8Resident(const uint8_t* table, const Q8Header& h,
                            bool stochastic, hipStream_t stream);
 
 }  // namespace adamw_q8
+
+// grad_norm.hip: the resident forms of the gradient norm.
+
+// Workgroups, and fp64 partials written, of launchGradSumsqResident over a
+// table of total_vblocks virtual blocks.
+int64_t gradSumsqResidentGrid(int64_t total_vblocks);
+
+// grad_sumsq_resident_kernel over a resident table on `stream`: one partial
+// sum of squares of the gradients per workgroup into partials[0 .. grid).
+// Nothing is launched for a table without virtual blocks.
+void launchGradSumsqResident(const uint8_t* table, int32_t n_tensors,
+                             int64_t total_vblocks, double* partials,
+                             hipStream_t stream);
+
+// The device address of an optional 1-element fp32 tensor on `device`
+// (`what` names it in the refusal), or nullptr for none.
+const float* deviceScalarPtr(const std::optional<at::Tensor>& scalar,
+                             const at::Device& device, const char* what);
 }  // namespace tdx

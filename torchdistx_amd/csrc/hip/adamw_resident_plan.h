@@ -46,10 +46,21 @@ class AdamWResidentPlan {
   // adamw_advance_kernel, then the kResident multi-tensor kernel, on the
   // current stream; nothing else. Exactly one of lr and lr_tensor counts:
   // lr_tensor (1-element fp32 on the parameters' device) when given.
+  // found_inf, validated like grad_scale (1-element fp32 on the parameters'
+  // device): where it is not zero both kernels leave everything, the step
+  // counts included, as it is.
   void step(double lr, const std::optional<at::Tensor>& lr_tensor,
             double beta1, double beta2, double eps, double weight_decay,
             const std::optional<at::Tensor>& grad_scale,
-            std::optional<int64_t> sr_seed);
+            std::optional<int64_t> sr_seed,
+            const std::optional<at::Tensor>& found_inf = std::nullopt);
+  // The number of fp64 partials grad_sumsq writes: the grid of its launch.
+  int64_t grad_grid() const;
+  // grad_sumsq_resident_kernel (grad_norm.hip) over the table on the
+  // current stream: the sums of squares of the gradients the table points
+  // at, one per workgroup, into partials[offset, offset + grad_grid()) of a
+  // contiguous fp64 tensor on the parameters' device. Allocates nothing.
+  void grad_sumsq(at::Tensor& partials, int64_t offset);
   // A host copy of the scalar slots as the last step left them:
   // (step_size fp32[n], bias_correction2_sqrt fp32[n], step int64[n],
   // decay fp32[1]). Synchronizes.

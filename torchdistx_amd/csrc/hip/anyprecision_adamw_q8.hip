@@ -402,9 +402,20 @@ __device__ __forceinline__ bool alignedTo(const void* p, uintptr_t bytes) {
 // kResident: blob is the resident table of adamw_q8_table.h; the step's
 // scalars come from the slots adamw_advance_kernel wrote before this launch
 // on the same stream (workgroup-uniform loads), not from the meta and h.
-template <bool kScaled, bool kStochastic, bool kResident = false>
+// kSkip == (h.found_inf != nullptr), resident only: a GradScaler's flag on
+// the device. One uniform load ahead of everything else; where it is not
+// zero the whole workgroup leaves before any tensor load or store, so the
+// step, captured or not, skips itself without the host learning of it.
+template <bool kScaled, bool kStochastic, bool kResident = false,
+          bool kSkip = false>
 __global__ __launch_bounds__(kQ8Threads) void adamw_q8_kernel(
     const uint8_t* __restrict__ blob, Q8Header h) {
+  static_assert(kResident || !kSkip, "only the resident step skips itself");
+  if constexpr (kSkip) {
+    if (*h.found_inf != 0.0f) {
+      return;
+    }
+  }
   using Meta =
       std::conditional_t<kResident, ResidentTensorMeta, Q8TensorMeta>;
   const int64_t* prefix = reinterpret_cast<const int64_t*>(blob);
@@ -672,13 +683,20 @@ void launchAdamwQ8Resident(const uint8_t* table, const Q8Header& h,
   const int grid = static_cast<int>(
       std::min<int64_t>(h.total_vblocks, kQ8MaxGrid));
   const bool scaled = h.grad_scale != nullptr;
-  auto* kernel =
-      stochastic ? (scaled ? adamw_q8_kernel<true, true, true>
-                           : adamw_q8_kernel<false, true, true>)
-                 : (scaled ? adamw_q8_kernel<true, false, true>
-                           : adamw_q8_kernel<false, false, true>);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kQ8Threads), 0, stream, table,
-                     h);
+  const bool skip = h.found_inf != nullptr;
+  using Kernel = void (*)(const uint8_t*, Q8Header);
+  // [skip][stochastic][scaled]
+  static const Kernel kernels[2][2][2] = {
+      {{adamw_q8_kernel<false, false, true>,
+        adamw_q8_kernel<true, false, true>},
+       {adamw_q8_kernel<false, true, true>,
+        adamw_q8_kernel<true, true, true>}},
+      {{adamw_q8_kernel<false, false, true, true>,
+        adamw_q8_kernel<true, false, true, true>},
+       {adamw_q8_kernel<false, true, true, true>,
+        adamw_q8_kernel<true, true, true, true>}}};
+  hipLaunchKernelGGL(kernels[skip][stochastic][scaled], dim3(grid),
+                     dim3(kQ8Threads), 0, stream, table, h);
   C10_HIP_KERNEL_LAUNCH_CHECK();
 }
 
@@ -777,6 +795,7 @@ void anyprecision_adamw_q8_step(
   h.decay = static_cast<float>(1.0 - lr * weight_decay);
   h.grad_scale = gradScalePtr(grad_scale, params[0]);
   h.sr_seed = stochastic ? static_cast<uint64_t>(*sr_seed) : 0;
+  h.found_inf = nullptr;
 
   const int grid =
       static_cast<int>(std::min<int64_t>(total_vblocks, kQ8MaxGrid));

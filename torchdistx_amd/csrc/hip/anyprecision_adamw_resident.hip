@@ -23,6 +23,11 @@
 // linear two-node graph, and a replay advances the counters as an eager
 // step does. Nothing is allocated, copied or synchronized in step(). The
 // plan keeps the parameters and states alive, not the gradients.
+//
+// Clipping and a GradScaler ride on the same table: grad_sumsq() runs the
+// norm pass of grad_norm.hip over the table's gradient fields, and step()
+// takes found_inf, a device flag under which both kernels return before
+// they touch anything.
 
 #include <hip/hip_runtime.h>
 
@@ -52,12 +57,19 @@ constexpr int kAdvanceThreads = 256;
 // AnyPrecisionAdamW.step forms on the host, 1 - beta1^t,
 // (1 - beta2^t)^(1/2) and lr / bias_correction1, each narrowed to fp32
 // once; an fp64 pow within a few ulp leaves them at most one fp32 rounding
-// boundary away from the host's.
+// boundary away from the host's. found_inf: nullptr, or the flag of a
+// skipped step (adamw_q8_table.h); a lane that reads it set leaves the
+// count and its slot alone, so a skipped step does not count, and the
+// stochastic-rounding bits, keyed by the count, do not advance either.
 __global__ __launch_bounds__(kAdvanceThreads) void adamw_advance_kernel(
     uint8_t* table, int n_tensors, double lr, const float* lr_ptr,
-    double beta1, double beta2, double weight_decay) {
+    double beta1, double beta2, double weight_decay,
+    const float* found_inf) {
   const int t = blockIdx.x * kAdvanceThreads + threadIdx.x;
   if (t >= n_tensors) {
+    return;
+  }
+  if (found_inf != nullptr && *found_inf != 0.0f) {
     return;
   }
   const ResidentTensorMeta* metas = reinterpret_cast<const ResidentTensorMeta*>(
@@ -274,12 +286,42 @@ void AdamWResidentPlan::rebind(const std::vector<at::Tensor>& grads) {
   upload(meta_bytes_);
 }
 
+int64_t AdamWResidentPlan::grad_grid() const {
+  return gradSumsqResidentGrid(total_vblocks_);
+}
+
+void AdamWResidentPlan::grad_sumsq(at::Tensor& partials, int64_t offset) {
+  const int64_t grid = grad_grid();
+  TORCH_CHECK(partials.is_cuda() &&
+                  partials.device() == params_[0].device() &&
+                  partials.scalar_type() == at::kDouble &&
+                  partials.is_contiguous() &&
+                  partials.unsafeGetTensorImpl()->has_storage(),
+              "AdamW resident plan: partials must be a contiguous float64 "
+              "tensor on the parameters' device");
+  TORCH_CHECK(offset >= 0 && offset <= partials.numel() &&
+                  grid <= partials.numel() - offset,
+              "AdamW resident plan: partials has ", partials.numel(),
+              " elements, the plan writes ", grid, " at offset ", offset);
+  if (grid == 0) {
+    return;  // every tensor is empty
+  }
+  auto stream = at::cuda::getCurrentCUDAStream();
+  usedOn(table_, last_stream_, stream);
+  launchGradSumsqResident(static_cast<const uint8_t*>(table_.const_data_ptr()),
+                          static_cast<int32_t>(params_.size()),
+                          total_vblocks_,
+                          partials.data_ptr<double>() + offset,
+                          stream.stream());
+}
+
 void AdamWResidentPlan::step(double lr,
                              const std::optional<at::Tensor>& lr_tensor,
                              double beta1, double beta2, double eps,
                              double weight_decay,
                              const std::optional<at::Tensor>& grad_scale,
-                             std::optional<int64_t> sr_seed) {
+                             std::optional<int64_t> sr_seed,
+                             const std::optional<at::Tensor>& found_inf) {
   const float* lr_ptr = nullptr;
   if (lr_tensor.has_value()) {
     const at::Tensor& l = *lr_tensor;
@@ -310,6 +352,7 @@ void AdamWResidentPlan::step(double lr,
   h.decay = 0.0f;  // the table's slot counts
   h.grad_scale = gradScalePtr(grad_scale, params_[0]);
   h.sr_seed = sr_seed.has_value() ? static_cast<uint64_t>(*sr_seed) : 0;
+  h.found_inf = deviceScalarPtr(found_inf, params_[0].device(), "found_inf");
 
   auto stream = at::cuda::getCurrentCUDAStream();
   usedOn(table_, last_stream_, stream);
@@ -317,7 +360,7 @@ void AdamWResidentPlan::step(double lr,
   hipLaunchKernelGGL(adamw_advance_kernel,
                      dim3((n + kAdvanceThreads - 1) / kAdvanceThreads),
                      dim3(kAdvanceThreads), 0, stream.stream(), table, n, lr,
-                     lr_ptr, beta1, beta2, weight_decay);
+                     lr_ptr, beta1, beta2, weight_decay, h.found_inf);
   C10_HIP_KERNEL_LAUNCH_CHECK();
   if (total_vblocks_ == 0) {
     // Every tensor is empty: only the counters advance.

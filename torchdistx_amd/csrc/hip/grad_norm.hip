@@ -26,6 +26,15 @@
 // operations, ds_swizzle, readlane), the four wave results meet in 32 bytes
 // of LDS behind one barrier, and thread 0 stores the workgroup's partial.
 // No atomics, no waiting between workgroups, no completion counters.
+//
+// Resident forms (docs/anyprecision_adamw.md, "Graph capture"):
+// grad_sumsq_resident_kernel is the same pass over the device table of an
+// AdamWResidentPlan, one launch per plan into its stretch of a partials
+// buffer the optimizer keeps; grad_norm_finalize_resident_kernel adds all
+// stretches and writes [norm, coef, grad_mult, found_inf], with the loss
+// scale of a GradScaler folded into the multiplier the step kernels load.
+// Nothing is allocated, copied or built per call, so the launches can be
+// captured, and replay with whatever gradients, scale and flag are there.
 
 #include <hip/hip_runtime.h>
 
@@ -34,6 +43,8 @@
 
 #include <cstring>
 #include <vector>
+
+#include "adamw_q8_table.h"
 
 // Compiled without the packed fp32 VALU instructions, as
 // anyprecision_adamw_q8.hip is (see there): device code below uses the
@@ -122,16 +133,31 @@ __device__ __forceinline__ double blockSum(double x, double* lds) {
   return total;
 }
 
-// blob layout: int64 prefix[n_tensors] then GradMeta[n_tensors]. No listed
-// tensor is empty. partials has gridDim.x entries; every workgroup owns at
-// least one virtual block and writes its own.
-__global__ __launch_bounds__(kThreads) void grad_sumsq_kernel(
-    const uint8_t* __restrict__ blob, int32_t n_tensors,
-    int64_t total_vblocks, double* __restrict__ partials) {
-  __shared__ double lds[kWaves];
-  const int64_t* prefix = reinterpret_cast<const int64_t*>(blob);
-  const GradMeta* metas =
-      reinterpret_cast<const GradMeta*>(blob + sizeof(int64_t) * n_tensors);
+// What the sum of squares needs of a table's per-tensor meta.
+struct GradRef {
+  const void* ptr;
+  int64_t n;
+  int32_t dtype;
+};
+
+__device__ __forceinline__ GradRef gradRef(const GradMeta& mt) {
+  return {mt.ptr, mt.n, mt.dtype};
+}
+__device__ __forceinline__ GradRef gradRef(
+    const adamw_q8::ResidentTensorMeta& mt) {
+  return {mt.grad, mt.n, mt.dt_grad};
+}
+
+// The workgroup's sum of squares over its virtual blocks of a table
+// (int64 prefix[n_tensors], then Meta[n_tensors]), valid in thread 0.
+template <class Meta>
+__device__ __forceinline__ double sumsqOfTable(const uint8_t* table,
+                                               int32_t n_tensors,
+                                               int64_t total_vblocks,
+                                               double* lds) {
+  const int64_t* prefix = reinterpret_cast<const int64_t*>(table);
+  const Meta* metas =
+      reinterpret_cast<const Meta*>(table + sizeof(int64_t) * n_tensors);
 
   double acc = 0.0;
   for (int64_t vb = blockIdx.x; vb < total_vblocks; vb += gridDim.x) {
@@ -145,7 +171,7 @@ __global__ __launch_bounds__(kThreads) void grad_sumsq_kernel(
         hi = mid - 1;
       }
     }
-    const GradMeta mt = metas[lo];
+    const GradRef mt = gradRef(metas[lo]);
     const int64_t e0 =
         (vb - prefix[lo]) * kEPB + static_cast<int64_t>(threadIdx.x) * 8;
     const int64_t left = mt.n - e0;
@@ -162,8 +188,37 @@ __global__ __launch_bounds__(kThreads) void grad_sumsq_kernel(
       acc = __builtin_fma(d, d, acc);
     }
   }
+  return blockSum(acc, lds);
+}
 
-  const double total = blockSum(acc, lds);
+// blob layout: int64 prefix[n_tensors] then GradMeta[n_tensors]. No listed
+// tensor is empty. partials has gridDim.x entries; every workgroup owns at
+// least one virtual block and writes its own.
+__global__ __launch_bounds__(kThreads) void grad_sumsq_kernel(
+    const uint8_t* __restrict__ blob, int32_t n_tensors,
+    int64_t total_vblocks, double* __restrict__ partials) {
+  __shared__ double lds[kWaves];
+  const double total =
+      sumsqOfTable<GradMeta>(blob, n_tensors, total_vblocks, lds);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = total;
+  }
+}
+
+// The same pass over the resident table of an AdamWResidentPlan
+// (adamw_q8_table.h): the virtual blocks, lanes and order of
+// grad_sumsq_kernel over the plan's gradients, read through the
+// {grad, n, dt_grad} of the metas the step kernel walks. No blob of its
+// own: a rebound plan is followed as it is, and a capture records one node
+// that needs no host work at replay. An empty tensor shares its prefix with
+// its successor and is never found. gridDim.x <= total_vblocks, one
+// partial per workgroup.
+__global__ __launch_bounds__(kThreads) void grad_sumsq_resident_kernel(
+    const uint8_t* __restrict__ table, int32_t n_tensors,
+    int64_t total_vblocks, double* __restrict__ partials) {
+  __shared__ double lds[kWaves];
+  const double total = sumsqOfTable<adamw_q8::ResidentTensorMeta>(
+      table, n_tensors, total_vblocks, lds);
   if (threadIdx.x == 0) {
     partials[blockIdx.x] = total;
   }
@@ -192,6 +247,44 @@ __global__ __launch_bounds__(kThreads) void grad_norm_finalize_kernel(
   }
 }
 
+// The finalize of the resident step, one workgroup: the partials of every
+// plan of the optimizer in the order of grad_norm_finalize_kernel, then
+// everything a captured step reads, formed in fp64 and narrowed once:
+//   out[0] = norm       sqrt(sumsq) / loss_scale, of the unscaled gradients
+//   out[1] = coef       the clip formula above on that norm; exactly 1
+//                       without clipping (`clip` false; n_partials is 0)
+//   out[2] = grad_mult  coef / loss_scale: what the step kernels multiply
+//                       each gradient by, one fp32 rounding as under coef
+//   out[3] = found_inf  1 if *found_inf_in is not zero, else 0
+// loss_scale and found_inf_in may be nullptr (scale 1, nothing found).
+__global__ __launch_bounds__(kThreads) void
+grad_norm_finalize_resident_kernel(const double* __restrict__ partials,
+                                   int n_partials, double max_norm, bool clip,
+                                   const float* __restrict__ loss_scale,
+                                   const float* __restrict__ found_inf_in,
+                                   float* __restrict__ out) {
+  __shared__ double lds[kWaves];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < n_partials; i += kThreads) {
+    acc += partials[i];
+  }
+  const double sumsq = blockSum(acc, lds);
+  if (threadIdx.x == 0) {
+    const double inv =
+        loss_scale != nullptr ? 1.0 / static_cast<double>(*loss_scale) : 1.0;
+    const double norm = __builtin_sqrt(sumsq) * inv;
+    double coef = 1.0;
+    if (clip) {
+      const double c = max_norm / (norm + 1e-6);
+      coef = c < 1.0 ? c : (c != c ? c : 1.0);
+    }
+    out[0] = static_cast<float>(norm);
+    out[1] = static_cast<float>(coef);
+    out[2] = static_cast<float>(coef * inv);
+    out[3] = found_inf_in != nullptr && *found_inf_in != 0.0f ? 1.0f : 0.0f;
+  }
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang attribute pop
 #endif
@@ -213,19 +306,24 @@ void checkPlainGpuTensor(const at::Tensor& t, const at::Device& device,
 // The device address of a step's optional gradient scale: one fp32 element
 // on the parameters' device (in practice the coef element of the tensor
 // grad_norm_clip_coef fills), or nullptr for none.
-const float* gradScalePtr(const std::optional<at::Tensor>& grad_scale,
-                          const at::Tensor& param) {
-  if (!grad_scale.has_value()) {
+const float* deviceScalarPtr(const std::optional<at::Tensor>& scalar,
+                             const at::Device& device, const char* what) {
+  if (!scalar.has_value()) {
     return nullptr;
   }
-  const at::Tensor& s = *grad_scale;
+  const at::Tensor& s = *scalar;
   TORCH_CHECK(s.is_cuda() && s.unsafeGetTensorImpl()->has_storage() &&
                   s.scalar_type() == at::kFloat && s.numel() == 1 &&
                   s.const_data_ptr() != nullptr,
-              "grad_scale must be a 1-element float32 GPU tensor");
-  TORCH_CHECK(s.device() == param.device(), "grad_scale is on ", s.device(),
-              ", the parameters are on ", param.device());
+              what, " must be a 1-element float32 GPU tensor");
+  TORCH_CHECK(s.device() == device, what, " is on ", s.device(),
+              ", the parameters are on ", device);
   return static_cast<const float*>(s.const_data_ptr());
+}
+
+const float* gradScalePtr(const std::optional<at::Tensor>& grad_scale,
+                          const at::Tensor& param) {
+  return deviceScalarPtr(grad_scale, param.device(), "grad_scale");
 }
 
 void grad_norm_clip_coef(std::vector<at::Tensor> grads, double max_norm,
@@ -301,5 +399,59 @@ void grad_norm_clip_coef(std::vector<at::Tensor> grads, double max_norm,
 }
 
 int64_t grad_norm_grid_cap() { return kGridCap; }
+
+static_assert(kEPB == adamw_q8::kQ8EPB,
+              "the resident table counts the norm pass's virtual blocks");
+
+int64_t gradSumsqResidentGrid(int64_t total_vblocks) {
+  return std::min<int64_t>(total_vblocks, kGridCap);
+}
+
+void launchGradSumsqResident(const uint8_t* table, int32_t n_tensors,
+                             int64_t total_vblocks, double* partials,
+                             hipStream_t stream) {
+  const int grid = static_cast<int>(gradSumsqResidentGrid(total_vblocks));
+  if (grid == 0) {
+    return;  // every tensor is empty: no partial, and no zero-block launch
+  }
+  hipLaunchKernelGGL(grad_sumsq_resident_kernel, dim3(grid), dim3(kThreads),
+                     0, stream, table, n_tensors, total_vblocks, partials);
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
+
+void grad_norm_finalize_resident(const std::optional<at::Tensor>& partials,
+                                 int64_t n_partials,
+                                 std::optional<double> max_norm,
+                                 const std::optional<at::Tensor>& loss_scale,
+                                 const std::optional<at::Tensor>& found_inf,
+                                 at::Tensor& out) {
+  TORCH_CHECK(!max_norm.has_value() || *max_norm > 0.0,
+              "grad norm: max_norm must be positive, got ", *max_norm);
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat &&
+                  out.numel() == 4,
+              "grad norm: out must be a 4-element float32 GPU tensor");
+  checkPlainGpuTensor(out, out.device(), "out");
+  TORCH_CHECK(n_partials >= 0 && n_partials < (int64_t{1} << 31),
+              "grad norm: n_partials out of range: ", n_partials);
+  const double* partials_ptr = nullptr;
+  if (n_partials > 0) {
+    TORCH_CHECK(partials.has_value() &&
+                    partials->scalar_type() == at::kDouble &&
+                    partials->numel() >= n_partials,
+                "grad norm: partials must be a float64 tensor of at least "
+                "n_partials elements");
+    checkPlainGpuTensor(*partials, out.device(), "partials");
+    partials_ptr = static_cast<const double*>(partials->const_data_ptr());
+  }
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(
+      grad_norm_finalize_resident_kernel, dim3(1), dim3(kThreads), 0,
+      stream.stream(), partials_ptr, static_cast<int>(n_partials),
+      max_norm.value_or(0.0), max_norm.has_value(),
+      deviceScalarPtr(loss_scale, out.device(), "loss_scale"),
+      deviceScalarPtr(found_inf, out.device(), "found_inf"),
+      static_cast<float*>(out.data_ptr()));
+  C10_HIP_KERNEL_LAUNCH_CHECK();
+}
 
 }  // namespace tdx

@@ -77,6 +77,13 @@ void grad_norm_clip_coef(std::vector<at::Tensor> grads, double max_norm,
 
 int64_t grad_norm_grid_cap();
 
+void grad_norm_finalize_resident(const std::optional<at::Tensor>& partials,
+                                 int64_t n_partials,
+                                 std::optional<double> max_norm,
+                                 const std::optional<at::Tensor>& loss_scale,
+                                 const std::optional<at::Tensor>& found_inf,
+                                 at::Tensor& out);
+
 std::tuple<std::vector<int64_t>, int64_t> slowmo_flat_layout(
     const std::vector<at::Tensor>& params);
 
@@ -193,21 +200,38 @@ PYBIND11_MODULE(_K, m) {
              std::variant<double, at::Tensor> lr, double beta1, double beta2,
              double eps, double weight_decay,
              std::optional<at::Tensor> grad_scale,
-             std::optional<int64_t> sr_seed) {
+             std::optional<int64_t> sr_seed,
+             std::optional<at::Tensor> found_inf) {
             const bool as_tensor = std::holds_alternative<at::Tensor>(lr);
             plan.step(as_tensor ? 0.0 : std::get<double>(lr),
                       as_tensor ? std::optional<at::Tensor>(
                                       std::get<at::Tensor>(lr))
                                 : std::nullopt,
-                      beta1, beta2, eps, weight_decay, grad_scale, sr_seed);
+                      beta1, beta2, eps, weight_decay, grad_scale, sr_seed,
+                      found_inf);
           },
           pybind11::arg("lr"), pybind11::arg("beta1"), pybind11::arg("beta2"),
           pybind11::arg("eps"), pybind11::arg("weight_decay"),
           pybind11::arg("grad_scale") = pybind11::none(),
           pybind11::arg("sr_seed") = pybind11::none(),
+          pybind11::arg("found_inf") = pybind11::none(),
           "One optimizer step on the current stream: the advance kernel "
           "(step += 1, bias corrections and decay from lr, a float or a "
-          "1-element float32 device tensor), then the multi-tensor update.")
+          "1-element float32 device tensor), then the multi-tensor update. "
+          "found_inf: optional 1-element float32 tensor on the parameters' "
+          "device; where it is not zero both kernels return before they "
+          "touch a step count, a parameter or a state.")
+      .def("grad_grid", &tdx::AdamWResidentPlan::grad_grid,
+           "The number of float64 partials grad_sumsq writes.")
+      .def(
+          "grad_sumsq",
+          [](tdx::AdamWResidentPlan& plan, at::Tensor partials,
+             int64_t offset) { plan.grad_sumsq(partials, offset); },
+          pybind11::arg("partials"), pybind11::arg("offset"),
+          "One launch on the current stream: the sums of squares of the "
+          "gradients the plan's table points at, accumulated in fp64, one "
+          "per workgroup into partials[offset : offset + grad_grid()]. "
+          "Allocates and copies nothing.")
       .def("scalars", &tdx::AdamWResidentPlan::scalars,
            "Host copies (step_size, bias_correction2_sqrt, step, decay) of "
            "the scalar slots as the last step left them; synchronizes.")
@@ -246,6 +270,23 @@ PYBIND11_MODULE(_K, m) {
       "accumulated in fp64, into out[0], and the clip_grad_norm_ coefficient "
       "min(max_norm / (norm + 1e-6), 1) into out[1]; out is a 2-element "
       "float32 tensor on the gradients' device. Nothing returns to the host.");
+  m.def(
+      "grad_norm_finalize_resident_",
+      [](std::optional<at::Tensor> partials, int64_t n_partials,
+         std::optional<double> max_norm, std::optional<at::Tensor> loss_scale,
+         std::optional<at::Tensor> found_inf, at::Tensor out) {
+        tdx::grad_norm_finalize_resident(partials, n_partials, max_norm,
+                                         loss_scale, found_inf, out);
+      },
+      pybind11::arg("partials"), pybind11::arg("n_partials"),
+      pybind11::arg("max_norm"), pybind11::arg("loss_scale"),
+      pybind11::arg("found_inf"), pybind11::arg("out"),
+      "One workgroup: adds partials[:n_partials] (AdamWResidentPlan."
+      "grad_sumsq) and writes out = [norm, coef, grad_mult, found_inf] "
+      "(4-element float32): the norm of the gradients divided by loss_scale, "
+      "the clip_grad_norm_ coefficient for max_norm (1 for None), coef / "
+      "loss_scale, and 1 where found_inf is not zero. loss_scale and "
+      "found_inf: optional 1-element float32 tensors on out's device.");
   m.def("grad_norm_grid_cap", &tdx::grad_norm_grid_cap,
         "Largest grid of the gradient sum-of-squares kernel; more virtual "
         "blocks than this are covered by its grid-stride loop.");

@@ -251,8 +251,18 @@ class AnyPrecisionAdamW(Optimizer):
             device-resident plan kept per param group, with no per-tensor
             host work: one kernel advances the step counts and forms the
             bias corrections on the device, the multi-tensor kernel applies
-            the update. Composes with Kahan summation, fp8 states,
-            stochastic rounding and, outside capture, ``max_grad_norm``.
+            the update. Composes with Kahan summation, fp8 states and
+            stochastic rounding. When every param group is capturable,
+            ``max_grad_norm`` and a ``torch.amp.GradScaler`` run inside
+            the step and can be captured with it: the norm is taken over
+            the resident plans, the loss scale is folded into the
+            multiplier the step kernels load, and a step whose
+            ``found_inf`` is set skips itself on the device without
+            counting. ``GradScaler.step`` then finds
+            ``_step_supports_amp_scaling`` and runs no unscale pass and no
+            ``found_inf.item()``; for a captured step set ``grad_scale``
+            and ``found_inf`` on the optimizer yourself, as 1-element fp32
+            device tensors that persist.
             Exists on the fused GPU path only — ``step`` raises
             ``RuntimeError`` where that path cannot run. Run one eager step
             before capturing and keep the gradient tensors in place
@@ -339,6 +349,19 @@ class AnyPrecisionAdamW(Optimizer):
         # had gradients when its device-resident plan was built, and the
         # plan (_K.AdamWResidentPlan).
         self._resident_plans = {}
+        # The resident clipped / amp step: the fp64 partials all plans
+        # share, the 4-element fp32 [norm, coef, grad_mult, found_inf], and
+        # the views of it handed out (grad_norm, grad_clip_coef and the two
+        # the step kernels read).
+        self._norm_buffers = (None, None, None)
+
+    @property
+    def _step_supports_amp_scaling(self):
+        """What ``torch.amp.GradScaler.step`` asks: whether ``step`` unscales
+        and skips by itself, from the ``grad_scale`` and ``found_inf``
+        tensors the scaler then sets on the optimizer. It does when every
+        param group is ``capturable=True``."""
+        return all(g.get("capturable", False) for g in self.param_groups)
 
     def load_state_dict(self, state_dict):
         """Base-class restore, then re-cast the optimizer states to their
@@ -489,10 +512,13 @@ class AnyPrecisionAdamW(Optimizer):
             cols[8].append(ordinal_of[id(p)])
         return _kernels.adamw_resident_plan(*cols)
 
-    def _capturable_group_step(self, index, group, first_ordinal, clip_on):
-        """One step of a capturable=True group: gather the gradients, check
-        them against the group's resident plan, launch it. clip_on(device)
-        is the clip coefficient there, or None."""
+    def _resident_plan_for(self, index, group, first_ordinal,
+                           refused="capturable=True: "):
+        """The resident plan of a capturable=True group, pointing at this
+        step's gradients: (plan, number of parameters, their device), or
+        None for a group without gradients. While the stream is
+        capturing a plan cannot be built or rebound: RuntimeError, headed by
+        `refused`, before anything is touched."""
         if self.use_fused is False:
             raise RuntimeError(
                 "capturable=True needs the fused AnyPrecisionAdamW step, "
@@ -500,7 +526,7 @@ class AnyPrecisionAdamW(Optimizer):
             )
         with_grad = [p for p in group["params"] if p.grad is not None]
         if not with_grad:
-            return
+            return None
         # Before the plan and the states: a refused step leaves nothing.
         lr = group["lr"]
         if isinstance(lr, torch.Tensor) and (
@@ -525,7 +551,7 @@ class AnyPrecisionAdamW(Optimizer):
             if with_grad[0].device.type == "cuda" and \
                     torch.cuda.is_current_stream_capturing():
                 raise RuntimeError(
-                    "capturable=True: the step's device-resident plan would "
+                    f"{refused}the step's device-resident plan would "
                     "have to be " + ("rebound to new gradient tensors"
                                      if same else "built")
                     + f" while the stream is capturing; {_CAPTURE_WARM_UP}"
@@ -537,13 +563,98 @@ class AnyPrecisionAdamW(Optimizer):
                     group, with_grad, first_ordinal)
                 unwrap = any(_is_dtensor(p) for p in with_grad)
                 self._resident_plans[index] = (with_grad, plan, unwrap)
+        return plan, len(with_grad), grads[0].device
+
+    @staticmethod
+    def _launch_resident_plan(plan, group, grad_scale, found_inf=None):
         beta1, beta2 = group["betas"]
         plan.step(
-            lr, beta1, beta2, group["eps"], group["weight_decay"],
-            clip_on(grads[0].device),
+            group["lr"], beta1, beta2, group["eps"], group["weight_decay"],
+            grad_scale,
             group["stochastic_rounding_seed"]
-            if group.get("stochastic_rounding", False) else None)
-        self._fused_steps += len(with_grad)
+            if group.get("stochastic_rounding", False) else None,
+            *(() if found_inf is None else (found_inf,)))
+
+    def _capturable_group_step(self, index, group, first_ordinal, clip_on):
+        """One step of a capturable=True group: gather the gradients, check
+        them against the group's resident plan, launch it. clip_on(device)
+        is the clip coefficient there, or None."""
+        got = self._resident_plan_for(index, group, first_ordinal)
+        if got is None:
+            return
+        plan, n, device = got
+        self._launch_resident_plan(plan, group, clip_on(device))
+        self._fused_steps += n
+
+    def _resident_scaled_step(self, with_grad, loss_scale, found_inf):
+        """One step with everything a captured step may need on the device
+        (docs/anyprecision_adamw.md, "Graph capture"): every group with
+        gradients is capturable=True and its gradients are on one GPU. With
+        max_grad_norm each group's resident plan leaves its fp64 partial
+        sums of squares in one shared buffer; a one-workgroup finalize folds
+        them, the clip formula and 1 / loss_scale into the multiplier the
+        step kernels load, next to found_inf, which makes the step skip
+        itself. Inside and outside capture the same launches."""
+        from torchdistx_amd import _kernels
+
+        clip = self.max_grad_norm is not None
+        device = _local_view(with_grad[0][0]).device
+        capturing = torch.cuda.is_current_stream_capturing()
+        refused = ("max_grad_norm cannot be captured before one eager step "
+                   "with it: " if clip else "capturable=True: ")
+        for name, t in (("grad_scale", loss_scale), ("found_inf", found_inf)):
+            if t is not None and not (
+                    isinstance(t, torch.Tensor) and t.device == device
+                    and t.dtype == torch.float32 and t.numel() == 1):
+                raise RuntimeError(
+                    f"{name} must be a 1-element float32 tensor on the "
+                    f"parameters' device {device}"
+                )
+        plans, ordinal = [], 0
+        for index, (group, ps) in enumerate(
+                zip(self.param_groups, with_grad)):
+            if ps:
+                plan, n, _ = self._resident_plan_for(
+                    index, group, ordinal, refused)
+                plans.append((plan, group, n))
+            ordinal += len(group["params"])
+
+        # One fp64 partial per workgroup of every plan's norm pass; its size
+        # changes only when a plan is built anew.
+        n_partials = sum(plan.grad_grid() for plan, _, _ in plans) \
+            if clip else 0
+        partials, out, views = self._norm_buffers
+        fits = (partials is not None and partials.device == device
+                and partials.numel() == n_partials)
+        if not fits or out is None or out.device != device:
+            if capturing:
+                raise RuntimeError(
+                    f"{refused}the gradient-norm buffers would have to be "
+                    "allocated while the stream is capturing; "
+                    f"{_CAPTURE_WARM_UP}"
+                )
+            if not fits:
+                partials = torch.empty(
+                    n_partials, dtype=torch.float64, device=device)
+            if out is None or out.device != device:
+                out = torch.tensor([0.0, 1.0, 1.0, 0.0], device=device)
+                views = (out[0], out[1], out[2:3], out[3:4])
+            self._norm_buffers = (partials, out, views)
+        norm, coef, mult, skip = views
+        # The same views every step: read them after a replay.
+        self.grad_norm, self.grad_clip_coef = norm, coef
+
+        offset = 0
+        if clip:
+            for plan, _, _ in plans:
+                plan.grad_sumsq(partials, offset)
+                offset += plan.grad_grid()
+        _kernels.grad_norm_finalize_resident_(
+            partials, offset, self.max_grad_norm, loss_scale, found_inf, out)
+        for plan, group, n in plans:
+            self._launch_resident_plan(
+                plan, group, mult, None if found_inf is None else skip)
+            self._fused_steps += n
 
     def _clip_norm_and_coef(self):
         """The 2-element fp32 tensor [norm, coef] of this step's gradients:
@@ -596,15 +707,60 @@ class AnyPrecisionAdamW(Optimizer):
             with torch.enable_grad():
                 closure()
 
+        # As torch's fused optimizers: set by torch.amp.GradScaler.step
+        # around this call (or by the user, as persistent tensors, for a
+        # captured step); grad_scale is None after an explicit unscale_.
+        loss_scale = getattr(self, "grad_scale", None)
+        found_inf = getattr(self, "found_inf", None)
+        amp = loss_scale is not None or found_inf is not None
+        if amp:
+            for index, group in enumerate(self.param_groups):
+                if not group.get("capturable", False):
+                    raise RuntimeError(
+                        "grad_scale / found_inf (torch.amp.GradScaler) are "
+                        "set on the optimizer, but param group "
+                        f"{index} is not capturable=True: unscaling and "
+                        "skipping inside the step exist on the resident "
+                        "path only"
+                    )
+        if amp or self.max_grad_norm is not None:
+            with_grad = [[p for p in g["params"] if p.grad is not None]
+                         for g in self.param_groups]
+            flat = [p for ps in with_grad for p in ps]
+            # The resident path: every group that has gradients is
+            # capturable, on one GPU. Everything else under max_grad_norm
+            # is refused or served below as before.
+            resident = (
+                bool(flat)
+                and all(g.get("capturable", False)
+                        for g, ps in zip(self.param_groups, with_grad) if ps)
+                and flat[0].device.type == "cuda"
+                and all(p.device == flat[0].device for p in flat)
+                and not (self.max_grad_norm is not None and any(
+                    _is_dtensor(p) or _is_dtensor(p.grad) for p in flat))
+            )
+            if resident:
+                self._resident_scaled_step(with_grad, loss_scale, found_inf)
+                return
+            if amp and flat:
+                raise RuntimeError(
+                    "grad_scale / found_inf (torch.amp.GradScaler) are set "
+                    "on the optimizer, but unscaling and skipping inside "
+                    "the step need every gradient on one GPU (and, next to "
+                    "max_grad_norm, no DTensor)"
+                )
+
         clip = None  # the coefficient as a 1-element tensor, per device
         if self.max_grad_norm is not None:
             if (any(g.get("capturable", False) for g in self.param_groups)
                     and torch.cuda.is_available()
                     and torch.cuda.is_current_stream_capturing()):
                 raise RuntimeError(
-                    "max_grad_norm cannot be captured in a graph yet: the "
-                    "gradient norm kernel builds its tensor table per call. "
-                    "Clip outside the captured region, or capture without "
+                    "max_grad_norm cannot be captured in a graph next to a "
+                    "param group that is not capturable=True, or with "
+                    "gradients on more than one GPU: the gradient norm "
+                    "kernel then builds its tensor table per call. Clip "
+                    "outside the captured region, or capture without "
                     "max_grad_norm"
                 )
             norm_coef = self._clip_norm_and_coef()
